@@ -1,6 +1,6 @@
 """bench.py — genes/sec of the end-to-end deseq2() hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--dump-outputs DIR]
 
 A "step" is one pass of the whole path (size factors -> MoM -> mu_hat -> genewise alpha ->
 trend/prior -> MAP alpha -> IRLS LFC -> Cook's (+ refit) -> Wald) over one synthetic count
@@ -292,6 +292,35 @@ def timed_steps(pipe, ctx, steps):
     return wall, gpu
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir, G):
+    """`--dump-outputs DIR`: the DeseqResult of the last timed step as DIR/<field>.npy (float64; flags as 0 / 1, scalars as
+    0-d arrays), so that two builds can be compared output for output on the same seeded matrix.  Above 64 MB in all, a
+    fixed seeded sample of the genes is written instead (DIR/gene_index.npy holds the sampled gene numbers)."""
+    arrays = {}
+    for name, v in vars(res).items():
+        if isinstance(v, (dict, str)) or v is None:
+            continue
+        a = np.asarray(v)
+        if a.dtype.kind not in "biuf":
+            continue
+        arrays[name] = np.array(a, dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        per_gene = sum(a.nbytes // G for a in arrays.values() if a.ndim and a.shape[0] == G) + 8  # (+ gene_index)
+        fixed = total - (per_gene - 8) * G + 4096 * (len(arrays) + 1)  # (+ the .npy headers, with room to spare)
+        keep = max(1, min(G, (DUMP_MAX_BYTES - fixed) // per_gene))
+        idx = np.sort(np.random.default_rng(0).choice(G, size=keep, replace=False))
+        arrays = {k: (a[idx] if a.ndim and a.shape[0] == G else a) for k, a in arrays.items()}
+        arrays["gene_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return sorted(arrays)
+
+
 def _mmm(v):
     v = np.asarray(v, float)
     return {"min": round(float(v.min()), 3), "median": round(float(np.median(v)), 3), "max": round(float(v.max()), 3)}
@@ -528,7 +557,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0)
     ap.add_argument("--no-extras", action="store_true", help="skip the summary-tail / shrinkage / c4-parity extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step as DIR/<field>.npy (float64; per-rank DIR/rank<r>/ "
+                         "when --gpus > 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(launch_local_ranks(args.gpus, sys.argv[1:]))
@@ -623,6 +657,10 @@ def main():
     dt = control.max_float(time.perf_counter() - t0)
     host_syncs_per_step = (int(ctx.lib.dsq_host_sync_count()) - syncs0 - 1) / max(args.steps, 1)
     barrier()
+    dumped = None
+    if args.dump_outputs:  # (before the profiled step below runs the path once more)
+        dump_dir = args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}")
+        dumped = {"dir": os.path.abspath(dump_dir), "arrays": dump_outputs(res, dump_dir, G)}
     if counting is not None:
         pipe.comm = comm
     klog_timed = pipe.kernel_log
@@ -835,6 +873,7 @@ def main():
         "cpu_baseline": cpu,
         "parity": parity,
         "stage_wall_ms_profiled_step": {k: round(v * 1e3, 3) for k, v in res_prof.timings.items()},
+        "dumped_outputs": dumped,
         "speedup_vs_cpu_baseline": round(value / cpu["value"], 1) if (cpu and parity_ok) else None,
         "speedup_note": "value / cpu_baseline.value: GPU resident rate over the oracle ('port') on this box's host cores; the "
                         "oracle is bit-identical to the unmodified reference and runs at 0.77-1.18 x its speed on the same "

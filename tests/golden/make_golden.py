@@ -385,7 +385,31 @@ def e2e_cases(di, which=None):
               f"refitted {int(r.refitted.sum())}, cooks_outlier {int(r.cooks_outlier.sum())}", flush=True)
 
 
+def inference_abc():
+    """inference_abc.json: the reference's abstract ``Inference`` interface (inference.py:9-362) as data - every abstract
+    method with its parameter names in order and the defaults it declares (tests/test_capi_exports.py)."""
+    import importlib.util
+    import inspect
+    import json
+
+    spec = importlib.util.spec_from_file_location("_ref_inference_abc", os.path.join(REF, "pydeseq2", "inference.py"))
+    mod = importlib.util.module_from_spec(spec)  # (numpy / pandas only)
+    spec.loader.exec_module(mod)
+    ref = mod.Inference
+    out = {}
+    for name in sorted(ref.__abstractmethods__):
+        sig = inspect.signature(getattr(ref, name))
+        out[name] = {"params": list(sig.parameters),
+                     "defaults": {k: p.default for k, p in sig.parameters.items() if p.default is not inspect.Parameter.empty}}
+    with open(os.path.join(HERE, "inference_abc.json"), "w") as fh:
+        json.dump(out, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "inference_abc":  # the reference's Inference interface (names, defaults)
+        inference_abc()
+        return
     ut, gs, pp, di = _import_reference()
     if len(sys.argv) > 1 and sys.argv[1] == "e2e":  # round 3: end-to-end outputs at the benchmark shapes
         e2e_cases(di, sys.argv[2:])

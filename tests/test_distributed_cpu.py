@@ -104,7 +104,9 @@ def _worker(rank, world, port, q):
 
 
 def test_world2_gloo_protocol_matches_single_process():
-    import torch.multiprocessing as mp
+    # plain multiprocessing: torch is imported by the workers only.  Imported here, its bundled HIP runtime and librccl would
+    # load into the test process, and the GPU tests after this one would run the engine's RCCL calls against them.
+    import multiprocessing as mp
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
@@ -283,3 +285,23 @@ def test_bench_hand_launcher_starts_one_process_per_rank(tmp_path):
     assert [g[0] for g in got] == ["0", "1", "2"] and all(g[2] == "3" and g[3] == "127.0.0.1" for g in got)
     assert len({g[4] for g in got}) == 1
     assert bench.launch_local_ranks(2, [str(tmp_path), "fail"], script=str(script)) == 3
+
+
+@pytest.mark.parametrize("config,genes,per_rank,block", [("c3", 0, 7500, 125), ("c5", 6000, 750, 625)])
+def test_bench_eight_rank_data_plan(config, genes, per_rank, block):
+    """What each rank of bench.py's `--gpus 8` strong-scaling job works on (BASELINE configs[2]: 60 000 x 1000, 7 500 genes
+    and a block of 125 samples per rank; a slice of configs[4]: 5000 samples in blocks of 625, the tiled generator building
+    only the rank's blocks): contiguous gene shards and sample blocks that cover the matrix once.  (c3 builds the whole
+    matrix per rank: its first and last rank only.)"""
+    import bench
+
+    G_cfg, N, _ = bench.CONFIGS[config]
+    G_total = genes or G_cfg
+    ranks = range(8) if config == "c5" else (0, 7)
+    for r in ranks:
+        counts, X, samp, G, Gt, gen = bench.plan_rank_data(config, genes, "strong", r, 8)
+        assert (G, Gt) == (per_rank, G_total) and counts.shape == (N, per_rank)
+        assert samp.shape == (block, G_total) and X.shape[0] == N
+        assert gen == ("tiled" if config == "c5" else "synth_counts")
+    blocks = [D.sample_block(r, 8, N) for r in range(8)]
+    assert blocks[0][0] == 0 and blocks[-1][1] == N and all(a[1] == b[0] for a, b in zip(blocks, blocks[1:]))

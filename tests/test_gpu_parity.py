@@ -966,12 +966,14 @@ def test_bench_two_ranks_strong_scaling_on_one_gpu():
     assert d["parity"]["ok"], d["parity"]
 
 
-@pytest.mark.parametrize("config,genes,per_rank,block", [("c3", 0, 7500, 125), ("c5", 6000, 750, 625)])
-def test_bench_eight_ranks_on_one_gpu(config, genes, per_rank, block):
-    """The driver's `--gpus 8` launch shape on a one-GPU box: eight ranks of bench.py share device 0 over the host-staged
-    transport - strong scaling of BASELINE configs[2] (60 000 x 1000: 7 500 genes and a block of 125 samples per rank)
-    and of a slice of configs[4] (5000 samples: blocks of 625; the tiled generator builds only the rank's blocks) -
-    three collectives per step and the single-GPU step's host synchronisations."""
+@pytest.mark.parametrize("config,genes,per_rank,block", [("c3", 0, 15000, 250), ("c5", 6000, 1500, 1250)])
+def test_bench_four_ranks_on_one_gpu(config, genes, per_rank, block):
+    """The driver's multi-rank launch on a one-GPU box: four ranks of bench.py share device 0 over the host-staged
+    transport - strong scaling of BASELINE configs[2] (60 000 x 1000: 15 000 genes and a block of 250 samples per rank)
+    and of a slice of configs[4] (5000 samples: blocks of 1250; the tiled generator builds only the rank's blocks) -
+    three collectives per step and the single-GPU step's host synchronisations.  Four ranks and this process keep the
+    number of processes holding the device at five; the `--gpus 8` data plan itself is checked on the host
+    (tests/test_distributed_cpu.py::test_bench_eight_rank_data_plan)."""
     import json
     import os
     import subprocess
@@ -981,13 +983,13 @@ def test_bench_eight_ranks_on_one_gpu(config, genes, per_rank, block):
     env = dict(os.environ, DSQ_BENCH_SHARE_GPU="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--config", config, "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--config", config, "--steps", "2", "--warmup", "1",
            "--no-cpu-baseline", "--no-extras"] + (["--genes", str(genes)] if genes else [])
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
-    assert d["n_gpus"] == 8 and d["scaling"] == "strong"
-    assert d["config"]["genes_per_gpu"] == per_rank and d["config"]["genes_total"] == 8 * per_rank
+    assert d["n_gpus"] == 4 and d["scaling"] == "strong"
+    assert d["config"]["genes_per_gpu"] == per_rank and d["config"]["genes_total"] == 4 * per_rank
     assert d["config"]["sample_block_rows"] == block
     assert d["collectives_per_step"] == 3, d["collectives_per_step"]
     assert d["value"] > 0 and d["ms_per_step"] > 0

@@ -73,9 +73,9 @@ BEGIN, END = "<!-- knobs:begin (generated by tools/knobs.py) -->", "<!-- knobs:e
 def scan():
     found = {}
     for base in ("pydeseq2_amd", "bench.py", "__graft_entry__.py"):
-        paths = [os.path.join(ROOT, base)] if base.endswith(".py") else [
+        paths = [os.path.join(ROOT, base)] if base.endswith(".py") else sorted(  # (sorted: os.walk order is the filesystem's)
             os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(ROOT, base)) for f in fs
-            if f.endswith((".py", ".hip", ".h"))]
+            if f.endswith((".py", ".hip", ".h")))
         for p in paths:
             for i, line in enumerate(open(p, errors="replace"), 1):
                 for m in re.finditer(r'(?:getenv\("|environ\.get\("|environ\[")(DSQ_[A-Z0-9_]+)"', line):
