@@ -199,13 +199,19 @@ DSQ_HD double frcp_g(double x) {
 
 // a / b to <= 1 ulp without the IEEE division's ~30 dependent instructions (v_rcp_f64 + Newton + one residual
 // correction): for scalar code whose latency matters (the optimisers between two evaluations), where b is a normal
-// non-zero number in every regular case; b = 0 or inf give what the division gives (through frcp_g).  Host: a / b.
+// non-zero number in every regular case.  Whatever leaves the correction NaN - b = 0 or inf, a NaN or infinite
+// operand, an overflowing quotient, and a subnormal b below 2^-1024 (its reciprocal overflows: a * inf gave inf or NaN
+// where a / b is finite, tests/test_devunit_math.py) - takes the IEEE division.  Host: a / b.
 DSQ_HD double fdiv(double a, double b) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const double r = frcp_g(b);
     const double q = a * r;
     const double q2 = fma(fma(-b, q, a), r, q);
-    return (q2 != q2) ? q : q2;
+    if (q2 != q2) {
+        DSQ_NO_SPECULATE;
+        return a / b;
+    }
+    return q2;
 #else
     return a / b;
 #endif

@@ -1,0 +1,137 @@
+"""ctypes front-end of the TEST-ONLY device build of dsq_math.h / dsq_wave.h (see devunit.hip).
+
+Every function takes numpy arrays, pads them to whole 256-thread blocks where the caller has not, runs one entry point
+(allocate, copy, launch, synchronise, free) and raises on a non-zero hipError_t."""
+import ctypes as C
+
+import numpy as np
+
+from .build import build
+
+_lib = None
+
+MATH_OPS = ["frcp", "frsq", "frcp_g", "fdiv", "flog", "flog_t", "flog1p", "flog1p_t", "fexp_t", "lgamma_pos",
+            "digamma_pos", "lgdg00", "lgdg10", "lgdg01", "lgdg11", "norm_sf", "stirling_big", "log_count"]
+WAVE_OPS = ["sum", "sumi", "maxi", "max", "excl_scan_i", "from_lane", "uniform", "readlane_d", "row_bcast", "any",
+            "hist_add", "slot_add", "slot_add_third", "cell_add"]
+SUM_N_K = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 16, 24, 48)
+BLOCK = 256
+
+
+class DevunitError(RuntimeError):
+    pass
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        _lib = C.CDLL(build())
+    return _lib
+
+
+def _p(a, t):
+    return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
+
+
+def _check(rc, what):
+    if rc != 0:
+        raise DevunitError(f"{what}: hipError_t {rc}")
+
+
+def _pad(x, dtype, fill):
+    """x flattened, padded with `fill` to a multiple of the block size (whole waves)."""
+    x = np.asarray(x, dtype=dtype).ravel()
+    n = max(BLOCK, -(-x.size // BLOCK) * BLOCK)
+    out = np.full(n, fill, dtype=dtype)
+    out[: x.size] = x
+    return out
+
+
+def math(op, x, y=None, pad=1.0):
+    """(first result, second result) of dsq_math op `op` (MATH_OPS) for every element of x (and y for fdiv)."""
+    xs = np.asarray(x, dtype=np.float64).ravel()
+    xp = _pad(xs, np.float64, pad)
+    yp = _pad(y, np.float64, 1.0) if y is not None else None
+    if yp is not None and yp.size != xp.size:
+        raise ValueError("x and y differ in size")
+    o1, o2 = np.zeros_like(xp), np.zeros_like(xp)
+    _check(lib().du_math(C.c_int(MATH_OPS.index(op)), _p(xp, C.c_double), _p(yp, C.c_double), _p(o1, C.c_double),
+                         _p(o2, C.c_double), C.c_int(xp.size)), f"du_math({op})")
+    return o1[: xs.size], o2[: xs.size]
+
+
+def tables():
+    """{'lgamma_int', 'log_int', 'log_tab', 'exp_tab'} as a kernel reads them (constant memory / LDS copies)."""
+    n = lib().du_tables_n()
+    o = np.full(n, np.nan)
+    _check(lib().du_tables(_p(o, C.c_double)), "du_tables")
+    return {"lgamma_int": o[:256], "log_int": o[256:512], "log_tab": o[512:768], "exp_tab": o[768:896]}
+
+
+def lgdiff(wave, y, a, grad=True, big=False):
+    """lgamma_digamma_diff<Wv, grad, big>: y is [genes][wave] counts, a one value per gene -> (dl, dd), same shape."""
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    G = y.shape[0]
+    if y.shape != (G, wave) or a.size != G:
+        raise ValueError("y must be [genes][wave], a one per gene")
+    per = BLOCK // wave
+    Gp = -(-G // per) * per
+    yp = np.full((Gp, wave), 256 if big else 0, np.int32)
+    yp[:G] = y
+    ap = np.ones(Gp)
+    ap[:G] = a
+    dl, dd = np.zeros(yp.size), np.zeros(yp.size)
+    _check(lib().du_lgdiff(C.c_int(wave), C.c_int(int(grad)), C.c_int(int(big)), _p(yp, C.c_int), _p(ap, C.c_double),
+                           _p(dl, C.c_double), _p(dd, C.c_double), C.c_int(yp.size)), "du_lgdiff")
+    return dl.reshape(Gp, wave)[:G], dd.reshape(Gp, wave)[:G]
+
+
+def irls_cst(y, a):
+    """irls_init's cst for one-sample genes: -[(lgamma(a) - lgamma(y + a)) + log(y!)] per (y, a)."""
+    y = np.asarray(y, dtype=np.int32).ravel()
+    G = y.size
+    Gp = -(-G // 4) * 4
+    yp = np.zeros(Gp, np.int32)
+    yp[:G] = y
+    ap = np.ones(Gp)
+    ap[:G] = np.broadcast_to(np.asarray(a, dtype=np.float64), (G,))
+    c = np.full(Gp, np.nan)
+    _check(lib().du_irls_cst(_p(yp, C.c_int), _p(ap, C.c_double), _p(c, C.c_double), C.c_int(64 * Gp)), "du_irls_cst")
+    return c[:G]
+
+
+def wave(wave, op, x=None, xi=None, even_only=False, nout=1, fill=np.nan, ifill=-7):
+    """Run the Wave policy's op (WAVE_OPS) on whole waves: x / xi hold n = multiple of 256 values (lane order).
+    Returns (double results, int results), each [nout][n]; entries the kernel did not write keep fill / ifill."""
+    n = (np.asarray(x) if x is not None else np.asarray(xi)).size
+    if n % BLOCK:
+        raise ValueError("n must be a multiple of 256")
+    xd = np.ascontiguousarray(x, dtype=np.float64).ravel() if x is not None else None
+    xin = np.ascontiguousarray(xi, dtype=np.int32).ravel() if xi is not None else None
+    o = np.full(n * nout, fill, dtype=np.float64)
+    oi = np.full(n * nout, ifill, dtype=np.int32)
+    _check(lib().du_wave(C.c_int(wave), C.c_int(WAVE_OPS.index(op)), C.c_int(int(even_only)), _p(xd, C.c_double),
+                         _p(xin, C.c_int), _p(o, C.c_double), _p(oi, C.c_int), C.c_int(n), C.c_int(nout)),
+           f"du_wave({wave}, {op})")
+    return o.reshape(nout, n), oi.reshape(nout, n)
+
+
+def sum_n(wave, x, even_only=False, fill=np.nan):
+    """x: [K][n] -> (sum_n<K> results, sum() of each value), both [K][n]."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    K, n = x.shape
+    o, r = np.full_like(x, fill), np.full_like(x, fill)
+    _check(lib().du_sumn(C.c_int(wave), C.c_int(K), C.c_int(int(even_only)), _p(x, C.c_double), _p(o, C.c_double),
+                         _p(r, C.c_double), C.c_int(n)), f"du_sumn({wave}, {K})")
+    return o, r
+
+
+def ksum(wave, x, even_only=False, fill=np.nan):
+    """x: [T][n] terms; lane i accumulates x[:, i] in a KSum -> (lane s, lane c, sum_comp result), each [n]."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    T, n = x.shape
+    ls, lc, o = np.full(n, fill), np.full(n, fill), np.full(n, fill)
+    _check(lib().du_ksum(C.c_int(wave), C.c_int(T), C.c_int(int(even_only)), _p(x, C.c_double), _p(ls, C.c_double),
+                         _p(lc, C.c_double), _p(o, C.c_double), C.c_int(n)), f"du_ksum({wave})")
+    return ls, lc, o

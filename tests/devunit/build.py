@@ -1,0 +1,63 @@
+"""Build tests/devunit/_devunit.so (hipcc, gfx950).  Test infrastructure, see devunit.hip.
+
+The compiler flags are the product's: CXXFLAGS and ARCH are read from pydeseq2_amd/csrc/Makefile, not restated, so
+that the device math is tested under the same -ffp-contract and -O level the kernels are built with."""
+import os
+import re
+import subprocess
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+SRC = os.path.join(HERE, "devunit.hip")
+OUT = os.path.join(HERE, "_devunit.so")
+INC = os.path.join(ROOT, "pydeseq2_amd", "csrc")
+MAKEFILE = os.path.join(INC, "Makefile")
+HIPCC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+
+
+def makefile_var(name):
+    """A variable of the Makefile's simple `NAME = value` / `NAME ?= value` assignments, $(NAME) references expanded."""
+    raw = {}
+    with open(MAKEFILE) as f:
+        for line in f:
+            m = re.match(r"^([A-Za-z_][A-Za-z0-9_]*)\s*\??=\s*(.*?)\s*$", line)
+            if m and m.group(1) not in raw:
+                raw[m.group(1)] = m.group(2)
+
+    def expand(v, depth=0):
+        if depth > 8:
+            raise RuntimeError(f"{MAKEFILE}: recursive variable in {v!r}")
+        return re.sub(r"\$\((\w+)\)", lambda m: expand(raw[m.group(1)], depth + 1), v)
+
+    return expand(raw[name])
+
+
+def cxxflags():
+    """The product's CXXFLAGS as a list (ARCH expanded)."""
+    return makefile_var("CXXFLAGS").split()
+
+
+def compile_cmd(out=OUT):
+    return [HIPCC, *cxxflags(), "-shared", "-I", INC, SRC, "-o", out]
+
+
+def asm_cmd(out):
+    """Device assembly of the library: shows which branches of the headers the device build took."""
+    return [HIPCC, *cxxflags(), "--cuda-device-only", "-S", "-I", INC, SRC, "-o", out]
+
+
+def build(force=False):
+    deps = [SRC, MAKEFILE] + [os.path.join(INC, f) for f in os.listdir(INC) if f.endswith(".h")]
+    deps.append(os.path.join(ROOT, "include", "deseq_hip.h"))
+    if not force and os.path.exists(OUT) and all(
+        os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps
+    ):
+        return OUT
+    tmp = os.path.join(HERE, f"_devunit.{os.getpid()}.so")  # atomic replace: a concurrent loader never sees half a file
+    subprocess.run(compile_cmd(tmp), check=True)
+    os.replace(tmp, OUT)
+    return OUT
+
+
+if __name__ == "__main__":
+    print(build(force=True))
