@@ -1,5 +1,8 @@
 // dsq_capi_inf.hip — the Inference-level entry points (dsq_inf_*: the drop-in boundary) and their device cache.
+#include <chrono>
+#include <list>
 #include <thread>
+#include <type_traits>
 
 #include "dsq_capi_internal.h"
 
@@ -19,13 +22,15 @@ struct PluginDesign {
         int mix_ready = 0;
         uint64_t tick = 0;
     };
-    std::vector<One> v;
+    std::list<One> v;  // (a One* handed out stays valid until its entry is replaced)
     uint64_t tick = 0;
 };
 
 void dsq_internal_destroy_plugin(dsq_ctx* ctx) {
     if (ctx->pc) {
-        dsq_pc::destroy(*ctx->pc);
+        dsq_pc::clear(*ctx->pc);
+        if (ctx->pc->d_acc) (void)hipFree(ctx->pc->d_acc);
+        if (ctx->pc->h_acc) (void)hipHostFree(ctx->pc->h_acc);
         delete ctx->pc;
         ctx->pc = nullptr;
     }
@@ -42,10 +47,25 @@ namespace {
 
 constexpr int kPluginDesigns = 4;
 
+struct Timer {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// the cache's device memory
+bool pc_hip_alloc(void** p, size_t bytes) {
+    if (hipMalloc(p, bytes) == hipSuccess) return true;
+    (void)hipGetLastError();  // (out of memory: the cache makes room and retries)
+    return false;
+}
+void pc_hip_free(void* p) { (void)hipFree(p); }
+
 dsq_pc::Cache& plugin_cache(dsq_ctx* ctx) {
     if (ctx->pc == nullptr) {
         ctx->pc = new dsq_pc::Cache();
         dsq_pc::Cache& c = *ctx->pc;
+        c.alloc = pc_hip_alloc;
+        c.free = pc_hip_free;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) total_b = (size_t)64 << 30;
         c.budget = total_b / 4;  // (MI355X: 72 GB; the matrices of BASELINE configs[4] at full size are 8.4 GB)
@@ -72,7 +92,7 @@ struct PcBuf {
     }
     hipError_t alloc(dsq_ctx* c, size_t bytes) {
         ctx = c;
-        return dsq_pc::take(plugin_cache(c), bytes, &p, &cap);
+        return dsq_pc::take(plugin_cache(c), bytes, &p, &cap) ? hipSuccess : hipErrorOutOfMemory;
     }
     void release() { p = nullptr; }  // (ownership went to a cache entry)
     template <class T>
@@ -96,65 +116,87 @@ int pc_upload_small(dsq_ctx* ctx, const void* src, size_t bytes, PcBuf& dst) {
     return DSQ_OK;
 }
 
-// verify mode: two gene-major device matrices ([G][ld_words] 32-bit words, n_words used per row) must agree word for word
-int pc_verify(dsq_ctx* ctx, const void* fresh, const void* resident, int ld_words, int n_words, int G) {
+// one reduction into the cache's 4-word accumulator: zeroed, `launch(d_acc)` enqueued, read back into c.h_acc (synchronises)
+template <class F>
+int pc_reduce(dsq_ctx* ctx, F launch) {
     dsq_pc::Cache& c = plugin_cache(ctx);
     DSQ_HIP(hipMemsetAsync(c.d_acc, 0, 4 * sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(dsq_pc::k_count_diff, dim3(std::min(G, 2048)), dim3(256), 0, ctx->stream, (const uint32_t*)fresh,
-                       (const uint32_t*)resident, ld_words, n_words, G, c.d_acc);
+    launch(c.d_acc);
     DSQ_HIP(hipGetLastError());
     DSQ_HIP(hipMemcpyAsync(c.h_acc, c.d_acc, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     DSQ_HIP(hipStreamSynchronize(ctx->stream));
-    ++c.st.verified;
-    if (c.h_acc[3] != 0)
-        return fail(ctx, DSQ_ERR_ARG, "plug-in cache: a matrix with the digest of a resident one differs from it "
-                                           "(DSQ_PLUGIN_CACHE_VERIFY)");
     return DSQ_OK;
 }
 
-// host count matrix -> resident gene-major int32 [G][ldn] (the cache's, not to be freed by the caller)
-int pc_counts(dsq_ctx* ctx, const void* counts, int count_type, int layout, int N, int G, int ldn,
-              const int32_t** d_y, dsq_pc::Entry** ent = nullptr) {
+// digest of a gene-major fp64 matrix [G][ldn] and whether some element is not positive, finite and normal: h_acc[0..2]
+int pc_digest_f64(dsq_ctx* ctx, const double* d, int ldn, int N, int G) {
+    return pc_reduce(ctx, [&](unsigned long long* acc) {
+        hipLaunchKernelGGL((dsq_pc::k_digest<double, true>), dim3(std::min(G, 2048)), dim3(256), 0, ctx->stream, d, ldn, N,
+                           G, acc);
+    });
+}
+
+// The resident copy of a host matrix with digest dg: gene-major [G][ldn] elements of T (int32 counts or fp64).  On a miss -
+// and on a hit in verify mode, whose fresh copy must then agree with the resident one word for word - `put(raw, hit)` sends
+// the N x G elements, in the caller's layout, to a device buffer and the transpose kernel lays them out gene-major.
+template <class T, class Put>
+int pc_matrix(dsq_ctx* ctx, const dsq_pc::Digest& dg, int layout, int N, int G, int ldn, Put put, dsq_pc::Entry** out) {
+    dsq_pc::Cache& c = plugin_cache(ctx);
+    constexpr bool f64 = std::is_same<T, double>::value;
+    dsq_pc::Entry* hit = dsq_pc::find(c, f64 ? dsq_pc::kF64 : dsq_pc::kCounts, N, G, dg);
+    *out = hit;
+    if (hit != nullptr && !c.verify) {
+        ++c.st.hits;
+        return DSQ_OK;
+    }
+    if (hit == nullptr) ++c.st.misses;
+    PcBuf raw, m;
+    DSQ_HIP(raw.alloc(ctx, (size_t)N * G * sizeof(T)));
+    DSQ_HIP(m.alloc(ctx, (size_t)G * ldn * sizeof(T)));
+    int rc;
+    if ((rc = put(raw.as<T>(), hit != nullptr))) return rc;
+    if (f64) DSQ_HIP(dsq::launch_transpose_f64(ctx->stream, raw.as<double>(), layout, N, G, m.as<double>(), ldn));
+    else DSQ_HIP(dsq::launch_transpose_counts(ctx->stream, raw.p, DSQ_I32, layout, N, G, m.as<int32_t>(), ldn,
+                                              (int*)ctx->d_scratch));
+    if (hit != nullptr) {  // DSQ_PLUGIN_CACHE_VERIFY: the digest matched - do the bytes?
+        const int w = (int)(sizeof(T) / 4);  // (32-bit words per element)
+        if ((rc = pc_reduce(ctx, [&](unsigned long long* acc) {
+                 hipLaunchKernelGGL(dsq_pc::k_count_diff, dim3(std::min(G, 2048)), dim3(256), 0, ctx->stream,
+                                    m.as<const uint32_t>(), (const uint32_t*)hit->d, w * ldn, w * N, G, acc);
+             })))
+            return rc;
+        ++c.st.verified;
+        if (c.h_acc[3] != 0)
+            return fail(ctx, DSQ_ERR_ARG, "plug-in cache: a matrix with the digest of a resident one differs from it "
+                                          "(DSQ_PLUGIN_CACHE_VERIFY)");
+        ++c.st.hits;
+        return DSQ_OK;
+    }
+    dsq_pc::Entry e;
+    e.kind = f64 ? dsq_pc::kF64 : dsq_pc::kCounts; e.N = N; e.G = G; e.ld = ldn; e.dg = dg; e.d = m.p; e.cap = m.cap;
+    m.release();
+    *out = dsq_pc::insert(c, e);
+    return DSQ_OK;
+}
+
+// host count matrix -> the cache entry of its resident gene-major int32 [G][ldn] (the cache's, not to be freed by the caller)
+int pc_counts(dsq_ctx* ctx, const void* counts, int count_type, int layout, int N, int G, int ldn, dsq_pc::Entry** out) {
     DSQ_CHECK_ARG(count_type == DSQ_I32 || count_type == DSQ_I64, "count_type");
     DSQ_CHECK_ARG(layout == DSQ_SAMPLE_MAJOR || layout == DSQ_GENE_MAJOR, "layout");
     dsq_pc::Cache& c = plugin_cache(ctx);
-    dsq_pc::Timer t;
+    Timer t;
     const dsq_pc::Digest dg = count_type == DSQ_I64
                                   ? dsq_pc::digest_host((const int64_t*)counts, layout, N, G, c.hash_threads)
                                   : dsq_pc::digest_host((const int32_t*)counts, layout, N, G, c.hash_threads);
     c.st.hash_ms += t.ms();
-    dsq_pc::Entry* hit = dsq_pc::find(c, dsq_pc::kCounts, N, G, dg);
-    if (hit != nullptr && !c.verify) {
-        ++c.st.hits;
-        *d_y = (const int32_t*)hit->d;
-        if (ent) *ent = hit;
-        return DSQ_OK;
-    }
-    if (hit == nullptr) ++c.st.misses;
-    PcBuf raw, y;
-    DSQ_HIP(raw.alloc(ctx, (size_t)N * G * sizeof(int32_t)));
-    DSQ_HIP(y.alloc(ctx, (size_t)G * ldn * sizeof(int32_t)));
-    int bad = 0, rc;
-    if ((rc = dsq_upload_counts_i32(ctx, counts, count_type, (size_t)N * G, raw.as<int32_t>(), &bad))) return rc;
-    if (bad) return fail(ctx, DSQ_ERR_RANGE, "counts must be integers in [0, 2^31)");
-    c.st.h2d_bytes += (size_t)N * G * (count_type == DSQ_I64 ? 8 : 4);
-    DSQ_HIP(dsq::launch_transpose_counts(ctx->stream, raw.p, DSQ_I32, layout, N, G, y.as<int32_t>(), ldn,
-                                         (int*)ctx->d_scratch));
-    if (hit != nullptr) {  // DSQ_PLUGIN_CACHE_VERIFY: the digest matched - do the bytes?
-        int rc2;
-        if ((rc2 = pc_verify(ctx, y.p, hit->d, ldn, N, G))) return rc2;
-        ++c.st.hits;
-        *d_y = (const int32_t*)hit->d;
-        if (ent) *ent = hit;
-        return DSQ_OK;
-    }
-    dsq_pc::Entry e;
-    e.kind = dsq_pc::kCounts; e.N = N; e.G = G; e.ld = ldn; e.dg = dg; e.d = y.p; e.cap = y.cap;
-    y.release();
-    dsq_pc::Entry* ne = dsq_pc::insert(c, e);
-    *d_y = (const int32_t*)ne->d;
-    if (ent) *ent = ne;
-    return DSQ_OK;
+    auto put = [&](int32_t* raw, bool) {
+        int bad = 0, rc;
+        if ((rc = dsq_upload_counts_i32(ctx, counts, count_type, (size_t)N * G, raw, &bad))) return rc;
+        if (bad) return fail(ctx, DSQ_ERR_RANGE, "counts must be integers in [0, 2^31)");
+        c.st.h2d_bytes += (size_t)N * G * (count_type == DSQ_I64 ? 8 : 4);
+        return (int)DSQ_OK;
+    };
+    return pc_matrix<int32_t>(ctx, dg, layout, N, G, ldn, put, out);
 }
 
 // host fp64 matrix -> resident gene-major [G][ldn]; need_positive: refuse a matrix with an element that is not positive,
@@ -163,41 +205,19 @@ int pc_counts(dsq_ctx* ctx, const void* counts, int count_type, int layout, int 
 int pc_f64(dsq_ctx* ctx, const double* src, int layout, int N, int G, int ldn, bool need_positive, const double** d_out) {
     DSQ_CHECK_ARG(layout == DSQ_SAMPLE_MAJOR || layout == DSQ_GENE_MAJOR, "layout");
     dsq_pc::Cache& c = plugin_cache(ctx);
-    dsq_pc::Timer t;
+    Timer t;
     const dsq_pc::Digest dg = dsq_pc::digest_host(src, layout, N, G, c.hash_threads);
     c.st.hash_ms += t.ms();
-    dsq_pc::Entry* e = dsq_pc::find(c, dsq_pc::kF64, N, G, dg);
-    if (e != nullptr && c.verify) {  // DSQ_PLUGIN_CACHE_VERIFY: upload again and compare with the resident copy
-        PcBuf raw, m;
-        DSQ_HIP(raw.alloc(ctx, (size_t)N * G * sizeof(double)));
-        DSQ_HIP(m.alloc(ctx, (size_t)G * ldn * sizeof(double)));
-        DSQ_HIP(hipMemcpyAsync(raw.p, src, (size_t)N * G * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        DSQ_HIP(dsq::launch_transpose_f64(ctx->stream, raw.as<double>(), layout, N, G, m.as<double>(), ldn));
-        int rc2;
-        if ((rc2 = pc_verify(ctx, m.p, e->d, 2 * ldn, 2 * N, G))) return rc2;
-    }
-    if (e != nullptr) {
-        ++c.st.hits;
-    } else {
-        ++c.st.misses;
-        PcBuf raw, m;
-        DSQ_HIP(raw.alloc(ctx, (size_t)N * G * sizeof(double)));
-        DSQ_HIP(m.alloc(ctx, (size_t)G * ldn * sizeof(double)));
-        DSQ_HIP(hipMemcpyAsync(raw.p, src, (size_t)N * G * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        c.st.h2d_bytes += (size_t)N * G * sizeof(double);
-        DSQ_HIP(dsq::launch_transpose_f64(ctx->stream, raw.as<double>(), layout, N, G, m.as<double>(), ldn));
-        dsq_pc::Entry ne;
-        ne.kind = dsq_pc::kF64; ne.N = N; ne.G = G; ne.ld = ldn; ne.dg = dg; ne.d = m.p; ne.cap = m.cap;
-        m.release();
-        e = dsq_pc::insert(c, ne);
-    }
+    auto put = [&](double* raw, bool verifying) {
+        DSQ_HIP(hipMemcpyAsync(raw, src, (size_t)N * G * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (!verifying) c.st.h2d_bytes += (size_t)N * G * sizeof(double);
+        return (int)DSQ_OK;
+    };
+    dsq_pc::Entry* e;
+    int rc;
+    if ((rc = pc_matrix<double>(ctx, dg, layout, N, G, ldn, put, &e))) return rc;
     if (need_positive && e->positive < 0) {
-        DSQ_HIP(hipMemsetAsync(c.d_acc, 0, 4 * sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL((dsq_pc::k_digest<double, true>), dim3(std::min(G, 2048)), dim3(256), 0, ctx->stream,
-                           (const double*)e->d, ldn, N, G, c.d_acc);
-        DSQ_HIP(hipGetLastError());
-        DSQ_HIP(hipMemcpyAsync(c.h_acc, c.d_acc, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        DSQ_HIP(hipStreamSynchronize(ctx->stream));
+        if ((rc = pc_digest_f64(ctx, (const double*)e->d, ldn, N, G))) return rc;
         e->positive = c.h_acc[2] ? 0 : 1;
     }
     if (need_positive && e->positive == 0)
@@ -212,12 +232,8 @@ int pc_f64(dsq_ctx* ctx, const double* src, int layout, int N, int G, int ldn, b
 int pc_adopt_f64(dsq_ctx* ctx, PcBuf& buf, int N, int G, int ldn) {
     dsq_pc::Cache& c = plugin_cache(ctx);
     if (!c.enabled) return DSQ_OK;  // (the buffer goes back to the free list with its owner)
-    DSQ_HIP(hipMemsetAsync(c.d_acc, 0, 4 * sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL((dsq_pc::k_digest<double, true>), dim3(std::min(G, 2048)), dim3(256), 0, ctx->stream,
-                       buf.as<double>(), ldn, N, G, c.d_acc);
-    DSQ_HIP(hipGetLastError());
-    DSQ_HIP(hipMemcpyAsync(c.h_acc, c.d_acc, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    DSQ_HIP(hipStreamSynchronize(ctx->stream));
+    int rc;
+    if ((rc = pc_digest_f64(ctx, buf.as<double>(), ldn, N, G))) return rc;
     dsq_pc::Digest dg;
     dg.a = c.h_acc[0]; dg.b = c.h_acc[1];
     if (dsq_pc::find(c, dsq_pc::kF64, N, G, dg) != nullptr) return DSQ_OK;  // (the same matrix is resident already)
@@ -309,13 +325,11 @@ int pc_design(dsq_ctx* ctx, const double* design, int N, int P, bool want_mix, P
         if (o.N == N && o.P == P && std::memcmp(o.X.data(), design, (size_t)N * P * sizeof(double)) == 0) hit = &o;
     if (hit == nullptr) {
         if ((int)D.v.size() >= kPluginDesigns) {  // replace the least recently used one
-            int lru = 0;
-            for (int i = 1; i < (int)D.v.size(); ++i)
-                if (D.v[(size_t)i].tick < D.v[(size_t)lru].tick) lru = i;
+            const auto lru = dsq_pc::lru(D.v);
             DSQ_HIP(hipStreamSynchronize(ctx->stream));
-            if (D.v[(size_t)lru].Xt) (void)hipFree(D.v[(size_t)lru].Xt);
-            dsq_mix_destroy(D.v[(size_t)lru].mix);
-            D.v.erase(D.v.begin() + lru);
+            if (lru->Xt) (void)hipFree(lru->Xt);
+            dsq_mix_destroy(lru->mix);
+            D.v.erase(lru);
         }
         PluginDesign::One o;
         o.N = N; o.P = P; o.ldx = pad16(N);
@@ -343,7 +357,7 @@ int pc_design(dsq_ctx* ctx, const double* design, int N, int P, bool want_mix, P
 
 // gene lists of the mixed-design dispersion kernel for a resident count matrix (kept with the cache entry)
 int pc_mix_lists(dsq_ctx* ctx, dsq_pc::Entry* e, int N, int G, int ldn) {
-    if (e->lists_ready) return DSQ_OK;
+    if (e->d_lists) return DSQ_OK;
     dsq_pc::Cache& c = plugin_cache(ctx);
     PcBuf flags;
     DSQ_HIP(flags.alloc(ctx, (size_t)G * sizeof(int32_t)));
@@ -357,13 +371,13 @@ int pc_mix_lists(dsq_ctx* ctx, dsq_pc::Entry* e, int N, int G, int ldn) {
         else lists[(size_t)(G - 1 - nw++)] = g;
     }
     std::reverse(lists.begin() + nr, lists.end());
-    void* d = nullptr;
-    size_t cap = 0;
-    DSQ_HIP(dsq_pc::take(c, (size_t)G * sizeof(int32_t), &d, &cap));
-    DSQ_HIP(hipMemcpyAsync(d, lists.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    PcBuf d;
+    DSQ_HIP(d.alloc(ctx, (size_t)G * sizeof(int32_t)));
+    DSQ_HIP(hipMemcpyAsync(d.p, lists.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     DSQ_HIP(hipStreamSynchronize(ctx->stream));  // the host list goes out of scope
-    e->d_lists = d; e->lists_cap = cap; e->n_rows = nr; e->n_waves = nw; e->lists_ready = 1;
-    c.resident += cap;
+    e->n_rows = nr; e->n_waves = nw;
+    dsq_pc::attach_lists(c, e, d.p, d.cap);
+    d.release();
     return DSQ_OK;
 }
 
@@ -420,12 +434,12 @@ int dsq_inf_grid_fit_alpha(dsq_ctx* ctx, const void* counts, int count_type, int
     const int ldn = pad16(N);
     int rc;
     if ((rc = pc_begin(ctx))) return rc;
-    const int32_t* d_y;
+    dsq_pc::Entry* y;
     const double* d_mu;
     PluginDesign::One* D;
     PcBuf a, work;
     if ((rc = pc_f64(ctx, mu, mu_layout, N, G, ldn, true, &d_mu))) return rc;
-    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &d_y))) return rc;
+    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &y))) return rc;
     if ((rc = pc_design(ctx, design, N, P, false, &D))) return rc;
     DSQ_HIP(a.alloc(ctx, (size_t)G * sizeof(double)));
     DSQ_HIP(work.alloc(ctx, (size_t)G * dsq::kAlphaGridWorkDoubles * sizeof(double)));
@@ -434,8 +448,8 @@ int dsq_inf_grid_fit_alpha(dsq_ctx* ctx, const void* counts, int count_type, int
     for (int g = 0; g < G; ++g) all[(size_t)g] = g;
     DSQ_HIP(hipMemcpyAsync(ctx->d_list, all.data(), (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     // the production fallback path: 100 wavefronts per gene and level (k_alpha_grid_eval)
-    DSQ_HIP(dsq::launch_alpha_grid(ctx->stream, d_y, d_mu, ldn, D->Xt, D->ldx, N, P, min_disp, max_disp, a.as<double>(),
-                                   ctx->d_list, G, work.as<double>()));
+    DSQ_HIP(dsq::launch_alpha_grid(ctx->stream, (const int32_t*)y->d, d_mu, ldn, D->Xt, D->ldx, N, P, min_disp, max_disp,
+                                   a.as<double>(), ctx->d_list, G, work.as<double>()));
     DSQ_HIP(hipMemcpyAsync(log_alpha_out, a.p, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     DSQ_HIP(hipStreamSynchronize(ctx->stream));
     // the production kernel stores alpha = exp(best grid point), which is what fit_alpha_mle needs
@@ -453,16 +467,16 @@ int dsq_inf_grid_fit_beta(dsq_ctx* ctx, const void* counts, int count_type, int 
     const int ldn = pad16(N);
     int rc;
     if ((rc = pc_begin(ctx))) return rc;
-    const int32_t* d_y;
+    dsq_pc::Entry* y;
     PluginDesign::One* D;
     PcBuf sf, d, b;
-    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &d_y))) return rc;
+    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &y))) return rc;
     if ((rc = pc_design(ctx, design, N, 2, false, &D))) return rc;
     if ((rc = pc_upload_small(ctx, size_factors, (size_t)N * sizeof(double), sf))) return rc;
     if ((rc = pc_upload_small(ctx, disp, (size_t)G * sizeof(double), d))) return rc;
     DSQ_HIP(b.alloc(ctx, (size_t)G * 2 * sizeof(double)));
-    DSQ_HIP(dsq::launch_grid_beta(ctx->stream, d_y, ldn, sf.as<double>(), D->Xt, D->ldx, N, G, d.as<double>(), min_mu,
-                                  min_beta, max_beta, grid_length, b.as<double>()));
+    DSQ_HIP(dsq::launch_grid_beta(ctx->stream, (const int32_t*)y->d, ldn, sf.as<double>(), D->Xt, D->ldx, N, G,
+                                  d.as<double>(), min_mu, min_beta, max_beta, grid_length, b.as<double>()));
     DSQ_HIP(hipMemcpyAsync(beta_out, b.p, (size_t)G * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     DSQ_HIP(hipStreamSynchronize(ctx->stream));
     return DSQ_OK;
@@ -498,15 +512,15 @@ int dsq_inf_lin_reg_mu(dsq_ctx* ctx, const void* counts, int count_type, int cou
     const int ldn = pad16(N);
     int rc;
     if ((rc = pc_begin(ctx))) return rc;
-    const int32_t* d_y;
+    dsq_pc::Entry* y;
     PluginDesign::One* D;
     PcBuf sf, mu;
-    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &d_y))) return rc;
+    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &y))) return rc;
     if ((rc = pc_design(ctx, design, N, P, false, &D))) return rc;
     if ((rc = pc_upload_small(ctx, size_factors, (size_t)N * sizeof(double), sf))) return rc;
     DSQ_HIP(mu.alloc(ctx, (size_t)G * ldn * sizeof(double)));
-    DSQ_HIP(dsq::launch_lin_mu(ctx->stream, d_y, ldn, sf.as<double>(), D->Xt, D->pinv, D->ldx, N, G, P, min_mu,
-                               mu.as<double>()));
+    DSQ_HIP(dsq::launch_lin_mu(ctx->stream, (const int32_t*)y->d, ldn, sf.as<double>(), D->Xt, D->pinv, D->ldx, N, G, P,
+                               min_mu, mu.as<double>()));
     if ((rc = pc_download_rows(ctx, mu_out, mu.as<double>(), ldn, N, G))) return rc;
     if ((rc = pc_adopt_f64(ctx, mu, N, G, ldn))) return rc;  // alpha_mle takes this matrix back (dds.py:778-785, 901-911)
     DSQ_HIP(hipStreamSynchronize(ctx->stream));
@@ -522,10 +536,10 @@ int dsq_inf_irls2(dsq_ctx* ctx, const void* counts, int count_type, int count_la
     const int ldn = pad16(N);
     int rc;
     if ((rc = pc_begin(ctx))) return rc;
-    const int32_t* d_y;
+    dsq_pc::Entry* y;
     PluginDesign::One* D;
     PcBuf sf, d, beta, mu, hat, conv;
-    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &d_y))) return rc;
+    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &y))) return rc;
     // mixed designs: the kernel family of the pipeline (csrc/dsq_mix.h)
     if ((rc = pc_design(ctx, design, N, P, true, &D))) return rc;
     if ((rc = pc_upload_small(ctx, size_factors, (size_t)N * sizeof(double), sf))) return rc;
@@ -536,9 +550,9 @@ int dsq_inf_irls2(dsq_ctx* ctx, const void* counts, int count_type, int count_la
     DSQ_HIP(conv.alloc(ctx, (size_t)G));
     dsq::IrlsExtras exi{};
     if (D->mix != nullptr) exi.mix = &D->mix->d;
-    rc = run_irls(ctx, d_y, ldn, sf.as<double>(), D->Xt, D->pinv, D->ldx, N, G, P, D->full_rank, d.as<double>(), min_mu,
-                  beta_tol, min_beta, max_beta, maxiter, beta.as<double>(), mu.as<double>(), hat.as<double>(),
-                  conv.as<uint8_t>(), nullptr, D->mix != nullptr ? &exi : nullptr, optimizer);
+    rc = run_irls(ctx, (const int32_t*)y->d, ldn, sf.as<double>(), D->Xt, D->pinv, D->ldx, N, G, P, D->full_rank,
+                  d.as<double>(), min_mu, beta_tol, min_beta, max_beta, maxiter, beta.as<double>(), mu.as<double>(),
+                  hat.as<double>(), conv.as<uint8_t>(), nullptr, D->mix != nullptr ? &exi : nullptr, optimizer);
     if (rc) return rc;
     DSQ_HIP(hipMemcpyAsync(beta_out, beta.p, (size_t)G * P * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     DSQ_HIP(hipMemcpyAsync(converged, conv.p, (size_t)G, hipMemcpyDeviceToHost, ctx->stream));
@@ -567,13 +581,12 @@ int dsq_inf_alpha_mle2(dsq_ctx* ctx, const void* counts, int count_type, int cou
     const int ldn = pad16(N);
     int rc;
     if ((rc = pc_begin(ctx))) return rc;
-    const int32_t* d_y;
+    dsq_pc::Entry* y;
     const double* d_mu;
-    dsq_pc::Entry* ye = nullptr;
     PluginDesign::One* D;
     PcBuf ah, a, conv;
     if ((rc = pc_f64(ctx, mu, mu_layout, N, G, ldn, true, &d_mu))) return rc;
-    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &d_y, &ye))) return rc;
+    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &y))) return rc;
     // mixed designs (categorical columns + up to three continuous covariates, csrc/dsq_mix.h): the kernel family of
     // the pipeline, here with mu gathered from the caller's matrix; genes with a count beyond its 16-bit staging stay on
     // the general kernel
@@ -585,12 +598,12 @@ int dsq_inf_alpha_mle2(dsq_ctx* ctx, const void* counts, int count_type, int cou
     dsq::AlphaExtras ex{};
     const bool mix = want_mix && D->mix != nullptr;
     if (mix) {
-        if ((rc = pc_mix_lists(ctx, ye, N, G, ldn))) return rc;
+        if ((rc = pc_mix_lists(ctx, y, N, G, ldn))) return rc;
         ex.mix = &D->mix->d;
-        ex.rows = (const int32_t*)ye->d_lists; ex.n_rows = ye->n_rows;
-        ex.waves = (const int32_t*)ye->d_lists + ye->n_rows; ex.n_waves = ye->n_waves;
+        ex.rows = (const int32_t*)y->d_lists; ex.n_rows = y->n_rows;
+        ex.waves = (const int32_t*)y->d_lists + y->n_rows; ex.n_waves = y->n_waves;
     }
-    if ((rc = run_alpha(ctx, d_y, d_mu, ldn, D->Xt, D->ldx, N, G, P, ah.as<double>(), min_disp, max_disp,
+    if ((rc = run_alpha(ctx, (const int32_t*)y->d, d_mu, ldn, D->Xt, D->ldx, N, G, P, ah.as<double>(), min_disp, max_disp,
                         prior_disp_var, cr_reg, prior_reg, a.as<double>(), conv.as<uint8_t>(), nullptr, nullptr,
                         DSQ_CONST_COMPUTE, mix ? &ex : nullptr, optimizer)))
         return rc;
@@ -618,19 +631,19 @@ int dsq_inf_lfc_shrink_nbinom_glm2(dsq_ctx* ctx, const void* counts, int count_t
     const int ldn = pad16(N);
     int rc;
     if ((rc = pc_begin(ctx))) return rc;
-    const int32_t* d_y;
+    dsq_pc::Entry* y;
     PluginDesign::One* D;
     PcBuf sz, off, b, ih, conv;
-    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &d_y))) return rc;
+    if ((rc = pc_counts(ctx, counts, count_type, count_layout, N, G, ldn, &y))) return rc;
     if ((rc = pc_design(ctx, design, N, P, false, &D))) return rc;
     if ((rc = pc_upload_small(ctx, size, (size_t)G * sizeof(double), sz))) return rc;
     if ((rc = pc_upload_small(ctx, offset, (size_t)N * sizeof(double), off))) return rc;
     DSQ_HIP(b.alloc(ctx, (size_t)G * P * sizeof(double)));
     DSQ_HIP(ih.alloc(ctx, (size_t)G * P * P * sizeof(double)));
     DSQ_HIP(conv.alloc(ctx, (size_t)G));
-    if ((rc = dsq_dev_lfc_shrink3(ctx, d_y, ldn, off.as<double>(), D->Xt, D->ldx, N, G, P, sz.as<double>(),
-                                  prior_no_shrink_scale, prior_scale, shrink_index, b.as<double>(), ih.as<double>(),
-                                  conv.as<uint8_t>(), nullptr, optimizer)))
+    if ((rc = dsq_dev_lfc_shrink3(ctx, (const int32_t*)y->d, ldn, off.as<double>(), D->Xt, D->ldx, N, G, P,
+                                  sz.as<double>(), prior_no_shrink_scale, prior_scale, shrink_index, b.as<double>(),
+                                  ih.as<double>(), conv.as<uint8_t>(), nullptr, optimizer)))
         return rc;
     DSQ_HIP(hipMemcpyAsync(beta_out, b.p, (size_t)G * P * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     DSQ_HIP(hipMemcpyAsync(inv_hessian_out, ih.p, (size_t)G * P * P * sizeof(double), hipMemcpyDeviceToHost,

@@ -31,7 +31,7 @@ extern std::atomic<unsigned long long> g_dsq_host_syncs;  // (defined in dsq_cap
 #include "../../include/deseq_hip.h"
 #include "dsq_launch.h"
 namespace dsq_pc {
-struct Cache;  // dsq_plugin_cache.h (dsq_capi_inf.hip only)
+struct Cache;  // dsq_plugin_pool.h (dsq_capi_inf.hip only)
 }
 
 // a mixed design on the device (dsq_mix_create): csrc/dsq_mix.h

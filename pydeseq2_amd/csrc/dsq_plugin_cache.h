@@ -12,24 +12,19 @@
 // matrix mutated in place has another digest.  Device buffers come from a size-matched free list (hipMalloc / hipFree of
 // 0.5 GB per call cost milliseconds and hipFree synchronises the device).
 //
-// Host glue only (no model math): included by dsq_capi_inf.hip.
+// This header holds what needs HIP: the digest (host and device) and the cache's kernels.  The bookkeeping - entries, LRU,
+// free list - is host code in dsq_plugin_pool.h.  Host glue only (no model math): included by dsq_capi_inf.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdint>
-#include <cstring>
 #include <thread>
-#include <utility>
 #include <vector>
 
-namespace dsq_pc {
+#include "dsq_plugin_pool.h"
 
-struct Digest {
-    uint64_t a = 0, b = 0;
-};
-inline bool operator==(const Digest& x, const Digest& y) { return x.a == y.a && x.b == y.b; }
+namespace dsq_pc {
 
 __host__ __device__ inline uint64_t mix64(uint64_t x) {  // (MurmurHash3's 64-bit finaliser: a bijection)
     x ^= x >> 33;
@@ -174,173 +169,5 @@ __global__ __launch_bounds__(256) void k_count_diff(const uint32_t* __restrict__
     for (int off = 32; off > 0; off >>= 1) d += __shfl_down(d, off);
     if ((threadIdx.x & 63) == 0 && d) atomicAdd(&acc[3], d);
 }
-
-enum Kind { kCounts = 0, kF64 = 1 };
-
-struct Entry {
-    int kind = 0, N = 0, G = 0, ld = 0;
-    Digest dg;
-    void* d = nullptr;
-    size_t cap = 0;
-    uint64_t tick = 0;
-    int positive = -1;  // fp64 matrices: every element positive, finite, normal?  -1: not checked yet
-    // counts: gene lists of the mixed-design dispersion kernel (genes with a count beyond its 16-bit staging stay on the
-    // general kernel), built on first use
-    int lists_ready = 0, n_rows = 0, n_waves = 0;
-    void* d_lists = nullptr;
-    size_t lists_cap = 0;
-};
-
-struct Stats {
-    uint64_t hits = 0, misses = 0, adopted = 0, evictions = 0, h2d_bytes = 0, d2h_bytes = 0, mallocs = 0, verified = 0;
-    double hash_ms = 0.0;
-};
-
-struct Cache {
-    bool enabled = true;
-    bool verify = false;  // DSQ_PLUGIN_CACHE_VERIFY: a hit is re-uploaded and compared with the resident copy
-    size_t budget = 0, resident = 0, pooled = 0;
-    uint64_t tick = 0, call_tick = 0;
-    int hash_threads = 32;
-    std::vector<Entry> ents;
-    std::vector<std::pair<size_t, void*>> free_bufs;
-    unsigned long long* d_acc = nullptr;  // 4 x u64: digest a, b, flag, spare
-    unsigned long long* h_acc = nullptr;  // page-locked mirror
-    Stats st;
-};
-
-inline hipError_t take(Cache& c, size_t bytes, void** p, size_t* cap) {
-    bytes = (bytes + 255) & ~(size_t)255;
-    if (bytes == 0) bytes = 256;
-    int best = -1;
-    for (int i = 0; i < (int)c.free_bufs.size(); ++i) {
-        const size_t k = c.free_bufs[(size_t)i].first;
-        if (k >= bytes && k <= 2 * bytes + 4096 && (best < 0 || k < c.free_bufs[(size_t)best].first)) best = i;
-    }
-    if (best >= 0) {
-        *cap = c.free_bufs[(size_t)best].first;
-        *p = c.free_bufs[(size_t)best].second;
-        c.pooled -= *cap;
-        c.free_bufs.erase(c.free_bufs.begin() + best);
-        return hipSuccess;
-    }
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {  // out of memory: drop the free list and retry ...
-        for (auto& f : c.free_bufs) (void)hipFree(f.second);
-        c.free_bufs.clear();
-        c.pooled = 0;
-        (void)hipGetLastError();
-        e = hipMalloc(p, bytes);
-    }
-    while (e != hipSuccess) {  // ... then the resident matrices the running call has not touched, least recently used first
-        int lru = -1;
-        for (int i = 0; i < (int)c.ents.size(); ++i)
-            if (c.ents[(size_t)i].tick <= c.call_tick && (lru < 0 || c.ents[(size_t)i].tick < c.ents[(size_t)lru].tick))
-                lru = i;
-        if (lru < 0) break;
-        Entry& v = c.ents[(size_t)lru];
-        c.resident -= v.cap + v.lists_cap;
-        (void)hipFree(v.d);
-        if (v.d_lists) (void)hipFree(v.d_lists);
-        c.ents.erase(c.ents.begin() + lru);
-        ++c.st.evictions;
-        (void)hipGetLastError();
-        e = hipMalloc(p, bytes);
-    }
-    if (e == hipSuccess) {
-        *cap = bytes;
-        ++c.st.mallocs;
-    }
-    return e;
-}
-
-inline void give(Cache& c, void* p, size_t cap) {
-    if (p == nullptr) return;
-    c.free_bufs.emplace_back(cap, p);
-    c.pooled += cap;
-    // free list and resident matrices share ONE budget (a context used to be able to pin twice the budget: the cache plus
-    // as much again on the free list); the free list keeps what the resident matrices leave of it
-    while (c.pooled + c.resident > c.budget && !c.free_bufs.empty()) {
-        int big = 0;
-        for (int i = 1; i < (int)c.free_bufs.size(); ++i)
-            if (c.free_bufs[(size_t)i].first > c.free_bufs[(size_t)big].first) big = i;
-        (void)hipFree(c.free_bufs[(size_t)big].second);  // (synchronises the device: rare)
-        c.pooled -= c.free_bufs[(size_t)big].first;
-        c.free_bufs.erase(c.free_bufs.begin() + big);
-    }
-}
-
-inline void drop_entry(Cache& c, int i) {
-    Entry& e = c.ents[(size_t)i];
-    c.resident -= e.cap + e.lists_cap;
-    give(c, e.d, e.cap);
-    give(c, e.d_lists, e.lists_cap);
-    c.ents.erase(c.ents.begin() + i);
-}
-
-inline Entry* find(Cache& c, int kind, int N, int G, const Digest& dg) {
-    for (Entry& e : c.ents)
-        if (e.kind == kind && e.N == N && e.G == G && e.dg == dg) {
-            e.tick = ++c.tick;
-            return &e;
-        }
-    return nullptr;
-}
-
-// a new resident matrix; least-recently-used entries that the running call has not touched make room
-inline Entry* insert(Cache& c, const Entry& e_in) {
-    Entry e = e_in;
-    e.tick = ++c.tick;
-    for (;;) {
-        if (c.resident + e.cap <= c.budget) break;
-        int lru = -1;
-        for (int i = 0; i < (int)c.ents.size(); ++i)
-            if (c.ents[(size_t)i].tick <= c.call_tick && (lru < 0 || c.ents[(size_t)i].tick < c.ents[(size_t)lru].tick))
-                lru = i;
-        if (lru < 0) break;  // everything resident belongs to this call: over budget until it ends
-        drop_entry(c, lru);
-        ++c.st.evictions;
-    }
-    c.resident += e.cap;
-    c.ents.push_back(e);
-    return &c.ents.back();
-}
-
-// start of an Inference-level call: entries touched from here on are not evicted by it; with the cache switched off
-// (or a budget the last call overran) what the previous call left goes back to the free list
-inline void begin_call(Cache& c) {
-    c.call_tick = c.tick;
-    if (!c.enabled) {
-        while (!c.ents.empty()) drop_entry(c, (int)c.ents.size() - 1);
-    } else {
-        while (c.resident > c.budget && !c.ents.empty()) {
-            int lru = 0;
-            for (int i = 1; i < (int)c.ents.size(); ++i)
-                if (c.ents[(size_t)i].tick < c.ents[(size_t)lru].tick) lru = i;
-            drop_entry(c, lru);
-            ++c.st.evictions;
-        }
-    }
-}
-
-inline void clear(Cache& c) {
-    while (!c.ents.empty()) drop_entry(c, (int)c.ents.size() - 1);
-    for (auto& f : c.free_bufs) (void)hipFree(f.second);
-    c.free_bufs.clear();
-    c.pooled = 0;
-}
-
-inline void destroy(Cache& c) {
-    clear(c);
-    if (c.d_acc) (void)hipFree(c.d_acc);
-    if (c.h_acc) (void)hipHostFree(c.h_acc);
-    c.d_acc = nullptr;
-    c.h_acc = nullptr;
-}
-
-struct Timer {
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
 
 }  // namespace dsq_pc

@@ -488,3 +488,75 @@ def lfc_fit(counts, sf, X, disp, cells=False, robust_disp=None, cutoff=0.0, cont
     if ck is not None:
         out["cooks"] = ck.T
     return out
+
+
+class PluginPool:
+    """The plug-in cache's bookkeeping (csrc/dsq_plugin_pool.h) over the fake device allocator of hostsim.cpp: `capacity`
+    bytes of "device memory", fail_next(k) makes the next k allocations fail.  One instance is live at a time."""
+
+    ENTRY_FIELDS = ("kind", "N", "G", "a", "b", "d", "cap", "tick", "d_lists", "lists_cap", "n_rows", "n_waves")
+    STATE_FIELDS = ("resident", "pooled", "budget", "entries", "evictions", "mallocs", "live_bytes", "live_blocks",
+                    "failed_allocs", "bad_frees")
+
+    def __init__(self, capacity, budget, enabled=True):
+        self.l = lib()
+        self.l.hs_pc_find.restype = C.c_void_p
+        self.l.hs_pc_insert.restype = C.c_void_p
+        self.l.hs_pc_reset(C.c_longlong(capacity), C.c_longlong(budget), C.c_int(int(enabled)))
+
+    def fail_next(self, k):
+        self.l.hs_pc_fail_next(C.c_int(k))
+
+    def set_budget(self, budget):
+        self.l.hs_pc_set_budget(C.c_longlong(budget))
+
+    def begin_call(self):
+        self.l.hs_pc_begin_call()
+
+    def clear(self):
+        self.l.hs_pc_clear()
+
+    def take(self, nbytes):
+        """(pointer, capacity) of a device buffer, or None when there is no memory"""
+        p, cap = C.c_void_p(), C.c_longlong()
+        ok = self.l.hs_pc_take(C.c_longlong(nbytes), C.byref(p), C.byref(cap))
+        return (p.value, cap.value) if ok else None
+
+    def give(self, p, cap):
+        self.l.hs_pc_give(C.c_void_p(p), C.c_longlong(cap))
+
+    def find(self, kind, N, G, a, b):
+        return self.l.hs_pc_find(C.c_int(kind), C.c_int(N), C.c_int(G), C.c_ulonglong(a), C.c_ulonglong(b))
+
+    def insert(self, kind, N, G, a, b, buf):
+        """a resident matrix in `buf`, a (pointer, capacity) from take(); returns the Entry*"""
+        return self.l.hs_pc_insert(C.c_int(kind), C.c_int(N), C.c_int(G), C.c_ulonglong(a), C.c_ulonglong(b),
+                                   C.c_void_p(buf[0]), C.c_longlong(buf[1]))
+
+    def attach_lists(self, e, buf, n_rows, n_waves):
+        self.l.hs_pc_attach_lists(C.c_void_p(e), C.c_void_p(buf[0]), C.c_longlong(buf[1]), C.c_int(n_rows),
+                                  C.c_int(n_waves))
+
+    def entries(self):
+        """the Entry* of every resident matrix, in storage order"""
+        n = self.l.hs_pc_entries(None, 0)
+        out = (C.c_void_p * max(n, 1))()
+        self.l.hs_pc_entries(out, C.c_int(n))
+        return [out[i] for i in range(n)]
+
+    def entry(self, e):
+        out = (C.c_ulonglong * 12)()
+        self.l.hs_pc_entry(C.c_void_p(e), out)
+        return dict(zip(self.ENTRY_FIELDS, list(out)))
+
+    def pool(self):
+        """the free list: [(capacity, pointer)] in list order"""
+        n = self.l.hs_pc_pool(None, None, 0)
+        sizes, ptrs = (C.c_ulonglong * max(n, 1))(), (C.c_void_p * max(n, 1))()
+        self.l.hs_pc_pool(sizes, ptrs, C.c_int(n))
+        return [(sizes[i], ptrs[i]) for i in range(n)]
+
+    def state(self):
+        out = (C.c_longlong * 10)()
+        self.l.hs_pc_state(out)
+        return dict(zip(self.STATE_FIELDS, list(out)))

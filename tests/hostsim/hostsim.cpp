@@ -8,7 +8,10 @@
 // never imported by the pydeseq2_amd package (whose ops fail loudly without the HIP .so).
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <map>
 #include <vector>
 
 #include "dsq_alpha.h"
@@ -17,6 +20,7 @@
 #include "dsq_irls.h"
 #include "dsq_lbfgsb.h"
 #include "dsq_lbfgsb_dense.h"
+#include "dsq_plugin_pool.h"
 #include "dsq_stats.h"
 #include "dsq_shrink.h"
 #include "dsq_trend.h"
@@ -577,6 +581,138 @@ int hs_lbfgsb_dense(fgn_cb cb, int n, double* x, const double* l, const double* 
     LbfgsbResult r = lbfgsb_dense<4>(fg, n, x, l, u, nbd, W);
     *f = r.f; *success = r.success; *nfev = r.nfev; *nit = r.nit; *status = r.status;
     return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ the plug-in cache's bookkeeping (dsq_plugin_pool.h)
+// One Cache over a fake device allocator: a byte capacity, "fail the next k allocations", every live block tracked (real heap
+// blocks, so that a sanitizer build sees a use after free).  A free of a pointer it did not hand out - or hands out no more -
+// is counted and reported on stderr; the tests require the count to stay 0.
+namespace {
+struct FakeDevice {
+    size_t capacity = 0, live_bytes = 0;
+    int fail_next = 0;
+    long allocs = 0, failed = 0, bad_frees = 0;
+    std::map<void*, size_t> live;
+};
+FakeDevice g_fake;
+dsq_pc::Cache* g_pc = nullptr;
+
+bool fake_alloc(void** p, size_t bytes) {
+    if (g_fake.fail_next > 0 || g_fake.live_bytes + bytes > g_fake.capacity) {
+        if (g_fake.fail_next > 0) --g_fake.fail_next;
+        ++g_fake.failed;
+        return false;
+    }
+    *p = std::malloc(bytes);
+    g_fake.live[*p] = bytes;
+    g_fake.live_bytes += bytes;
+    ++g_fake.allocs;
+    return true;
+}
+
+void fake_free(void* p) {
+    auto it = g_fake.live.find(p);
+    if (it == g_fake.live.end()) {
+        std::fprintf(stderr, "hostsim fake device: free of %p, which is not a live allocation\n", p);
+        ++g_fake.bad_frees;
+        return;
+    }
+    g_fake.live_bytes -= it->second;
+    g_fake.live.erase(it);
+    std::free(p);
+}
+}  // namespace
+
+extern "C" {
+
+// a fresh cache (the previous one cleared and deleted) over a fresh fake device of `capacity` bytes
+void hs_pc_reset(long long capacity, long long budget, int enabled) {
+    if (g_pc) {
+        dsq_pc::clear(*g_pc);
+        delete g_pc;
+    }
+    for (auto& b : g_fake.live) std::free(b.first);  // (what a test held itself)
+    g_fake = FakeDevice();
+    g_fake.capacity = (size_t)capacity;
+    g_pc = new dsq_pc::Cache();
+    g_pc->alloc = fake_alloc;
+    g_pc->free = fake_free;
+    g_pc->budget = (size_t)budget;
+    g_pc->enabled = enabled != 0;
+}
+
+void hs_pc_fail_next(int k) { g_fake.fail_next = k; }
+void hs_pc_set_budget(long long budget) { g_pc->budget = (size_t)budget; }
+void hs_pc_begin_call() { dsq_pc::begin_call(*g_pc); }
+void hs_pc_clear() { dsq_pc::clear(*g_pc); }
+
+int hs_pc_take(long long bytes, void** p, long long* cap) {
+    size_t c = 0;
+    const bool ok = dsq_pc::take(*g_pc, (size_t)bytes, p, &c);
+    *cap = (long long)c;
+    return ok ? 1 : 0;
+}
+
+void hs_pc_give(void* p, long long cap) { dsq_pc::give(*g_pc, p, (size_t)cap); }
+
+void* hs_pc_find(int kind, int N, int G, unsigned long long a, unsigned long long b) {
+    dsq_pc::Digest dg;
+    dg.a = a; dg.b = b;
+    return dsq_pc::find(*g_pc, kind, N, G, dg);
+}
+
+// a resident matrix in a buffer from hs_pc_take (the cache owns it from here on)
+void* hs_pc_insert(int kind, int N, int G, unsigned long long a, unsigned long long b, void* d, long long cap) {
+    dsq_pc::Entry e;
+    e.kind = kind; e.N = N; e.G = G; e.ld = N; e.dg.a = a; e.dg.b = b; e.d = d; e.cap = (size_t)cap;
+    return dsq_pc::insert(*g_pc, e);
+}
+
+void hs_pc_attach_lists(void* e, void* p, long long cap, int n_rows, int n_waves) {
+    dsq_pc::Entry* x = (dsq_pc::Entry*)e;
+    x->n_rows = n_rows; x->n_waves = n_waves;
+    dsq_pc::attach_lists(*g_pc, x, p, (size_t)cap);
+}
+
+// the entries in storage order (no tick is touched); returns how many there are
+int hs_pc_entries(void** out, int max) {
+    int n = 0;
+    for (auto& e : g_pc->ents) {
+        if (n < max) out[n] = &e;
+        ++n;
+    }
+    return n;
+}
+
+// fields of an entry: kind, N, G, dg.a, dg.b, d, cap, tick, d_lists, lists_cap, n_rows, n_waves
+void hs_pc_entry(const void* e, unsigned long long* out) {
+    const dsq_pc::Entry& x = *(const dsq_pc::Entry*)e;
+    const unsigned long long v[12] = {(unsigned long long)x.kind, (unsigned long long)x.N, (unsigned long long)x.G,
+                                      x.dg.a, x.dg.b, (unsigned long long)(uintptr_t)x.d, x.cap, x.tick,
+                                      (unsigned long long)(uintptr_t)x.d_lists, x.lists_cap,
+                                      (unsigned long long)x.n_rows, (unsigned long long)x.n_waves};
+    std::memcpy(out, v, sizeof(v));
+}
+
+// the pooled buffers (size, pointer) in free-list order; returns how many there are
+int hs_pc_pool(unsigned long long* sizes, void** ptrs, int max) {
+    int n = 0;
+    for (auto& f : g_pc->free_bufs) {
+        if (n < max) { sizes[n] = f.first; ptrs[n] = f.second; }
+        ++n;
+    }
+    return n;
+}
+
+// resident, pooled, budget, entries, evictions, mallocs, fake live bytes, fake live blocks, fake failed allocs, bad frees
+void hs_pc_state(long long* out) {
+    const long long v[10] = {(long long)g_pc->resident, (long long)g_pc->pooled, (long long)g_pc->budget,
+                             (long long)g_pc->ents.size(), (long long)g_pc->st.evictions, (long long)g_pc->st.mallocs,
+                             (long long)g_fake.live_bytes, (long long)g_fake.live.size(), g_fake.failed,
+                             g_fake.bad_frees};
+    std::memcpy(out, v, sizeof(v));
 }
 
 }  // extern "C"
