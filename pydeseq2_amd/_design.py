@@ -4,7 +4,7 @@ from __future__ import annotations
 import numpy as np
 
 
-MAX_DESIGN_COLUMNS = 48  # DSQ_MAX_P of include/deseq_hip.h
+MAX_DESIGN_COLUMNS = 128  # DSQ_MAX_P of include/deseq_hip.h
 
 
 def pad16(n: int) -> int:
@@ -33,7 +33,7 @@ class DesignPack:
         self.N, self.P = X.shape
         if self.P > MAX_DESIGN_COLUMNS:
             # documented limit: the reference's per-gene solvers take any width (utils.py:345-371, numpy / scipy
-            # on a p x p system); here the p x p workspaces of the widest kernel family live in a wavefront's LDS segment
+            # on a p x p system); here the widest kernel family (dsq_wider.h) sizes its LDS and device-memory slots for 128
             raise ValueError(f"The design matrix has {self.P} columns; the device kernels take at most "
                              f"{MAX_DESIGN_COLUMNS} (DSQ_MAX_P).  Merge or drop design variables.")
         self.ldx = pad16(self.N)

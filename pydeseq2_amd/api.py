@@ -19,6 +19,7 @@ import pandas as pd
 
 from . import summary as _summary
 from ._design import DesignPack
+from . import _lib
 from ._lib import Context
 from .pipeline import DeseqPipeline
 
@@ -965,6 +966,10 @@ class DeseqStats:
             raise KeyError(f"The coeff argument '{coeff}' should be one the LFC columns. "
                            f"The available LFC coeffs are {self.LFC.columns[1:]}.")
         j = self.LFC.columns.get_loc(coeff)
+        P = self.LFC.shape[1]
+        if P > _lib.DSQ_SHRINK_MAX_P:
+            raise ValueError(f"lfc_shrink: the design matrix has {P} columns; apeGLM shrinkage takes at most "
+                             f"{_lib.DSQ_SHRINK_MAX_P} (DSQ_SHRINK_MAX_P) design columns.")
         if not hasattr(self, "SE"):
             self.run_wald_test()
         r = self.dds._res

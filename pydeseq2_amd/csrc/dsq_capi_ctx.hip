@@ -38,7 +38,12 @@ int dsq_set_deferred(dsq_ctx* ctx, int on) {
 void dsq_destroy(dsq_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
+    // the device-memory slots of the wider kernels that ran on this context's streams (before the streams go)
+    for (hipStream_t s : {ctx->stream, ctx->main_stream, ctx->side_stream, ctx->small_stream, ctx->lfc_stream})
+        if (s != nullptr) dsq::wider_release(s);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
+    if (ctx->d_ridge_wide) (void)hipFree(ctx->d_ridge_wide);
+    if (ctx->h_ridge_wide) (void)hipHostFree(ctx->h_ridge_wide);
     if (ctx->d_counter) (void)hipFree(ctx->d_counter);
     if (ctx->d_list) (void)hipFree(ctx->d_list);
     if (ctx->d_ws) (void)hipFree(ctx->d_ws);

@@ -503,7 +503,9 @@ int dsq_dev_lfc_fit2(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_
         ex.any_all = d_any_all; ex.any_use = d_any_use; ex.any_use_nr = d_any_use_nr; ex.few_above = d_few_above;
     }
     if (h_ridge != nullptr) {
-        double* d_ridge = ctx->d_scratch + 1664;  // (behind the trend kernels' partials and outputs)
+        double* d_ridge;  // (behind the trend kernels' partials and outputs; wider designs: ridge_stage)
+        double* h_stage;
+        { const int rc = ridge_stage(ctx, P, &d_ridge, &h_stage); if (rc != DSQ_OK) return fail(ctx, rc, "ridge staging: out of memory"); }
         double* d_contrast = d_ridge + P * P;  // (behind the matrix: both travel in one copy)
         // via page-locked memory: the caller's arrays may be temporaries, and a pageable source would make the
         // copy (and the launch behind it) wait for the host
@@ -517,7 +519,6 @@ int dsq_dev_lfc_fit2(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_
                               (ctx->lfc_phase == 2 || (ctx->lfc_phase == 1 && ctx->lfc_prepared_wald &&
                                                        ctx->lfc_prepared_N == N && ctx->lfc_prepared_P == P));
         if (!in_place) {
-            double* h_stage = (double*)(ctx->h_pin + (P <= 32 ? 16 : 4096));
             std::memcpy(h_stage, h_ridge, (size_t)P * P * sizeof(double));
             std::memcpy(h_stage + P * P, h_contrast, (size_t)P * sizeof(double));
             DSQ_HIP(hipMemcpyAsync(d_ridge, h_stage, (size_t)(P * P + P) * sizeof(double), hipMemcpyHostToDevice,
@@ -580,8 +581,10 @@ int dsq_dev_wald(dsq_ctx* ctx, const double* d_mu, int ldn, const double* d_sf, 
                  double* d_se) {
     DSQ_CHECK_ARG(P >= 1 && P <= DSQ_MAX_P, "P out of range");
     DSQ_CHECK_ARG(alt >= 0 && alt <= 4, "unknown alternative hypothesis");
-    double* d_ridge = ctx->d_scratch + 1664;  // (behind the trend kernels' partials and outputs)
-    double* d_contrast = d_ridge + DSQ_MAX_P * DSQ_MAX_P;
+    double* d_ridge;  // (behind the trend kernels' partials and outputs; wider designs: ridge_stage)
+    double* h_unused;
+    { const int rc = ridge_stage(ctx, P, &d_ridge, &h_unused); if (rc != DSQ_OK) return fail(ctx, rc, "ridge staging: out of memory"); }
+    double* d_contrast = d_ridge + (P <= 48 ? 48 * 48 : P * P);
     DSQ_HIP(hipMemcpyAsync(d_ridge, h_ridge, (size_t)P * P * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     DSQ_HIP(hipMemcpyAsync(d_contrast, h_contrast, (size_t)P * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     DSQ_HIP(hipStreamSynchronize(ctx->stream));
@@ -688,8 +691,9 @@ int dsq_lfc_prepare(dsq_ctx* ctx, const double* d_sf, int N, const double* h_rid
     DSQ_HIP(hipMemsetAsync(ctx->d_counter + 8, 0, 2 * sizeof(int32_t), ctx->stream));
     ctx->lfc_prepared_wald = 0;
     if (h_ridge != nullptr && h_contrast != nullptr) {
-        double* d_ridge = ctx->d_scratch + 1664;
-        double* h_stage = (double*)(ctx->h_pin + (P <= 32 ? 16 : 4096));
+        double* d_ridge;
+        double* h_stage;
+        { const int rc = ridge_stage(ctx, P, &d_ridge, &h_stage); if (rc != DSQ_OK) return fail(ctx, rc, "ridge staging: out of memory"); }
         std::memcpy(h_stage, h_ridge, (size_t)P * P * sizeof(double));
         std::memcpy(h_stage + P * P, h_contrast, (size_t)P * sizeof(double));
         DSQ_HIP(hipMemcpyAsync(d_ridge, h_stage, (size_t)(P * P + P) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));

@@ -70,6 +70,8 @@ struct dsq_ctx {
     int deferred = 0;             // dsq_set_deferred: second passes of small batches enqueued without a host round trip
     int32_t* h_pin = nullptr;     // 64 KiB of page-locked host memory: counters read back / small arguments sent (ints [0, 16): counters;
                                   // [16, 3072) + [4096, 16384): ridge / contrast staging up to p = 48; [3072, 4096): trend outputs)
+    double* d_ridge_wide = nullptr;  // ridge / contrast of designs wider than 48 columns (DSQ_MAX_P^2 + DSQ_MAX_P doubles,
+    double* h_ridge_wide = nullptr;  // device and page-locked host, allocated on first use: ridge_stage)
     void* d_ws = nullptr;         // workspace of the rare second-pass kernels (grown on demand, never shrunk)
     size_t ws_cap = 0;
     void* d_resume = nullptr;     // parked optimiser states + gene list of the two-phase dispersion launch (grow-only)
@@ -120,6 +122,28 @@ namespace {
 
 constexpr size_t kScratchBytes = 32 * 1024;  // doubles [0, 1664): scalars, trend partials and outputs; [1664, 4096): ridge + contrast (48 x 48 + 48)
 constexpr int kDeferredMaxGenes = 2048;  // deferred second passes are launched for every gene of the batch
+
+// where the ridge matrix and the contrast of a Wald statistic travel: up to 48 columns the scratch block (d, from
+// double 1664) and the page-locked block (h, from int 16 or 4096), as ever; wider designs a pair of buffers of their own
+inline int ridge_stage(dsq_ctx* ctx, int P, double** d, double** h) {
+    if (P <= 48) {
+        *d = ctx->d_scratch + 1664;
+        *h = (double*)(ctx->h_pin + (P <= 32 ? 16 : 4096));
+        return DSQ_OK;
+    }
+    const size_t bytes = (size_t)(DSQ_MAX_P * DSQ_MAX_P + DSQ_MAX_P) * sizeof(double);
+    if (ctx->d_ridge_wide == nullptr && hipMalloc((void**)&ctx->d_ridge_wide, bytes) != hipSuccess) {
+        ctx->d_ridge_wide = nullptr;
+        return DSQ_ERR_NOMEM;
+    }
+    if (ctx->h_ridge_wide == nullptr && hipHostMalloc((void**)&ctx->h_ridge_wide, bytes, hipHostMallocDefault) != hipSuccess) {
+        ctx->h_ridge_wide = nullptr;
+        return DSQ_ERR_NOMEM;
+    }
+    *d = ctx->d_ridge_wide;
+    *h = ctx->h_ridge_wide;
+    return DSQ_OK;
+}
 
 int fail(dsq_ctx* c, int code, const std::string& msg) {
     if (c) {

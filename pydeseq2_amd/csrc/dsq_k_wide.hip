@@ -1,6 +1,6 @@
 // dsq_k_wide.hip — kernels of the run-time-P path (dsq_wide.h): designs wider than the register path's 12 columns
-// (up to kWideMaxP = 48), and — optionally — narrower designs without cell structure, whose p(p+1) register
-// accumulators spill.  One gene per wavefront; the wave's p x p matrices, the staged design chunk and the small
+// (up to kWideMaxP = 48; the launchers forward wider designs to dsq_k_wider.hip), and — optionally — narrower designs
+// without cell structure, whose p(p+1) register accumulators spill.  One gene per wavefront; the wave's p x p matrices, the staged design chunk and the small
 // vectors live in a wave-private segment of dynamic LDS whose size follows P (1, 2 or 4 waves per workgroup);
 // X^T W X is accumulated by v_mfma_f64_16x16x4_f64 (or from per-cell sums for cell designs).
 #include "dsq_dispatch.h"
@@ -69,6 +69,9 @@ hipError_t launch_wide_mom(hipStream_t st, const int32_t* y, int ldn, const doub
                            double min_mu, double* normed_mean, double* rough, double* moments, double* mom,
                            double* mu, double* coef, const double* d_s_mean_inv) {
     if (G <= 0) return hipSuccess;
+    if (P > kWideMaxP)
+        return launch_wider_mom(st, y, ldn, sf, Xt, pinvXt, ldx, N, G, P, min_disp, max_disp, min_mu, normed_mean, rough,
+                                moments, mom, mu, coef, d_s_mean_inv);
     const WideGeom ge = wide_geom(P);
     set_smem(k_mom_wide, ge.per_wave * ge.wpb);
     hipLaunchKernelGGL(k_mom_wide, dim3((G + ge.wpb - 1) / ge.wpb), dim3(64 * ge.wpb), ge.per_wave * ge.wpb, st, y,
@@ -106,6 +109,7 @@ __global__ __launch_bounds__(256) void k_rough_normed_wide(const double* __restr
 hipError_t launch_wide_rough_normed(hipStream_t st, const double* normed, int ldn, const double* Xt,
                                     const double* pinvXt, int ldx, int N, int G, int P, double* out) {
     if (G <= 0) return hipSuccess;
+    if (P > kWideMaxP) return launch_wider_rough_normed(st, normed, ldn, Xt, pinvXt, ldx, N, G, P, out);
     const WideGeom ge = wide_geom(P);
     set_smem(k_rough_normed_wide, ge.per_wave * ge.wpb);
     hipLaunchKernelGGL(k_rough_normed_wide, dim3((G + ge.wpb - 1) / ge.wpb), dim3(64 * ge.wpb), ge.per_wave * ge.wpb,
@@ -188,6 +192,9 @@ hipError_t launch_wide_alpha(hipStream_t st, const int32_t* y, const double* mu,
                              int32_t* nfev, double* nll_const, int const_mode, const CellDesign* cells) {
     if (G <= 0) return hipSuccess;
     if (nll_const == nullptr) const_mode = DSQ_CONST_COMPUTE;
+    if (P > kWideMaxP)
+        return launch_wider_alpha(st, y, mu, ldn, Xt, ldx, N, G, P, alpha_hat, min_disp, max_disp, prior_var, cr_reg,
+                                  prior_reg, alpha, conv, nfev, nll_const, const_mode);
     CellDesign cd{};
     if (cells != nullptr) cd = *cells;
     const WideGeom ge = wide_geom(P);
@@ -202,6 +209,8 @@ hipError_t launch_wide_alpha_grid(hipStream_t st, const int32_t* y, const double
                                   int ldx, int N, int P, double min_disp, double max_disp, double* alpha,
                                   const int32_t* list, int n_list) {
     if (n_list <= 0) return hipSuccess;
+    if (P > kWideMaxP)
+        return launch_wider_alpha_grid(st, y, mu, ldn, Xt, ldx, N, P, min_disp, max_disp, alpha, list, n_list);
     const WideGeom ge = wide_geom(P);
     set_smem(k_alpha_grid_wide, ge.per_wave * ge.wpb);
     hipLaunchKernelGGL(k_alpha_grid_wide, dim3((n_list + ge.wpb - 1) / ge.wpb), dim3(64 * ge.wpb),
@@ -312,6 +321,9 @@ hipError_t launch_wide_irls(hipStream_t st, const int32_t* y, int ldn, const dou
                             int maxiter, double* beta, double* mu, double* hat, uint8_t* conv, int32_t* iters,
                             int32_t* fb_count, int32_t* fb_list, const IrlsExtras* extras) {
     if (G <= 0) return hipSuccess;
+    if (P > kWideMaxP)
+        return launch_wider_irls(st, y, ldn, sf, lsf, Xt, pinvXt, ldx, N, G, P, full_rank, disp, min_mu, beta_tol, min_beta,
+                                 max_beta, maxiter, beta, mu, hat, conv, iters, fb_count, fb_list, extras);
     IrlsExtras ex{};
     if (extras != nullptr) ex = *extras;
     const WideGeom ge = wide_geom(P);
@@ -328,6 +340,9 @@ hipError_t launch_wide_irls_rescue(hipStream_t st, const int32_t* y, int ldn, co
                                    double max_beta, int maxiter, double* beta, double* mu, double* hat, uint8_t* conv,
                                    int32_t* iters, const int32_t* fb_list, int n_fb, const IrlsExtras* extras) {
     if (n_fb <= 0) return hipSuccess;
+    if (P > kWideMaxP)
+        return launch_wider_irls_rescue(st, y, ldn, sf, lsf, Xt, pinvXt, ldx, N, P, full_rank, disp, min_mu, beta_tol,
+                                        min_beta, max_beta, maxiter, beta, mu, hat, conv, iters, fb_list, n_fb, extras);
     IrlsExtras ex{};
     if (extras != nullptr) ex = *extras;
     ex.cells = CellDesign{};  // the rescue of a diverged gene runs the general evaluation
@@ -363,6 +378,8 @@ hipError_t launch_wide_irls_layers(hipStream_t st, const int32_t* y, int ldn, co
                                    int ldx, int N, int G, int P, const double* disp, const double* beta, double min_mu,
                                    double* mu, double* hat) {
     if (G <= 0) return hipSuccess;
+    if (P > kWideMaxP)
+        return launch_wider_irls_layers(st, y, ldn, sf, Xt, ldx, N, G, P, disp, beta, min_mu, mu, hat);
     const WideGeom ge = wide_geom(P);
     set_smem(k_irls_layers_wide, ge.per_wave * ge.wpb);
     hipLaunchKernelGGL(k_irls_layers_wide, dim3((G + ge.wpb - 1) / ge.wpb), dim3(64 * ge.wpb), ge.per_wave * ge.wpb,
@@ -394,6 +411,9 @@ hipError_t launch_wide_wald(hipStream_t st, const double* mu, int ldn, const dou
                             const double* d_contrast, double lfc_null, int alt, double* pvals, double* stats,
                             double* se) {
     if (G <= 0) return hipSuccess;
+    if (P > kWideMaxP)
+        return launch_wider_wald(st, mu, ldn, sf, Xt, ldx, N, G, P, disp, beta, d_ridge, d_contrast, lfc_null, alt, pvals,
+                                 stats, se);
     const WideGeom ge = wide_geom(P);
     set_smem(k_wald_wide, ge.per_wave * ge.wpb);
     hipLaunchKernelGGL(k_wald_wide, dim3((G + ge.wpb - 1) / ge.wpb), dim3(64 * ge.wpb), ge.per_wave * ge.wpb, st, mu,

@@ -33,13 +33,20 @@ DSQ_HD int wide_work_doubles(int P) {
     return 5 * P * wide_ld(P) + rows * kWideXsLd + 2 * 64 + 8 * kWideMaxP + 4 * kMaxCells;
 }
 
-struct WideWork {
+// The workspace of one gene.  MP = kWideMaxP: everything in one LDS segment (bind).  MP > kWideMaxP (dsq_wider.h):
+// the five p x p matrices and the Gram tile accumulators `gacc` in a slot of device memory, the rest in LDS
+// (bind_split).  The functions below take either; only WideGram's device branch and the rescue's L-BFGS-B
+// workspace depend on MP.
+template <int MP>
+struct WideWorkT {
+    static constexpr int kMaxP = MP;
     int P, ld, rows;
     double *M, *dM, *L, *Li, *inv;  // P x P, leading dimension ld
     double* xs;                     // [rows][kWideXsLd] chunk of the design (rows >= P are zero)
     double* w;                      // [2][64] per-sample weights of the chunk
-    double* vec;                    // [8][kWideMaxP] small vectors (beta, rhs, ...)
+    double* vec;                    // [8][MP] small vectors (beta, rhs, ...)
     double *acc, *tab;              // [2][kMaxCells] each: cell path
+    double* gacc = nullptr;         // MP > kWideMaxP: [2][tiles][64][4] Gram accumulators (WideGram)
     DSQ_HD void bind(double* base, int P_) {
         P = P_; ld = wide_ld(P_); rows = ((P_ + 15) / 16) * 16;
         const int m = P * ld;
@@ -47,16 +54,30 @@ struct WideWork {
         xs = inv + m;
         w = xs + rows * kWideXsLd;
         vec = w + 2 * 64;
-        acc = vec + 8 * kWideMaxP;
+        acc = vec + 8 * MP;
         tab = acc + 2 * kMaxCells;
     }
-    DSQ_HD double* v(int k) const { return vec + k * kWideMaxP; }
+    // gacc and the matrices in `mem` (32-byte aligned), the rest in `lds`
+    static constexpr int kGaccDoubles = 2 * (MP / 16) * (MP / 16 + 1) / 2 * 256;
+    DSQ_HD void bind_split(double* lds, double* mem, int P_) {
+        P = P_; ld = wide_ld(P_); rows = ((P_ + 15) / 16) * 16;
+        const int m = P * ld;
+        gacc = mem;
+        M = gacc + kGaccDoubles; dM = M + m; L = dM + m; Li = L + m; inv = Li + m;
+        xs = lds;
+        w = xs + rows * kWideXsLd;
+        vec = w + 2 * 64;
+        acc = vec + 8 * MP;
+        tab = acc + 2 * kMaxCells;
+    }
+    DSQ_HD double* v(int k) const { return vec + k * MP; }
 };
+using WideWork = WideWorkT<kWideMaxP>;
 
 // ------------------------------------------------------------------ LDS linear algebra (lane-parallel)
 // L = chol(A + diag_add I): row-parallel right-looking factorisation, same operation order per entry as chol<P>
-template <class Wv>
-DSQ_HD void wide_chol(const WideWork& W, const double* A, double* L, double diag_add) {
+template <class Wv, int MP>
+DSQ_HD void wide_chol(const WideWorkT<MP>& W, const double* A, double* L, double diag_add) {
     const int P = W.P, ld = W.ld;
     for (int j = 0; j < P; ++j) {
         double d = A[j * ld + j] + diag_add;
@@ -74,16 +95,16 @@ DSQ_HD void wide_chol(const WideWork& W, const double* A, double* L, double diag
     }
 }
 
-template <class Wv>
-DSQ_HD double wide_logdet(const WideWork& W, const double* L) {
+template <class Wv, int MP>
+DSQ_HD double wide_logdet(const WideWorkT<MP>& W, const double* L) {
     double s = 0.0;
     for (int j = 0; j < W.P; ++j) s += log(L[j * W.ld + j]);
     return 2.0 * s;
 }
 
 // solve (L L^T) x = b in place (b: P doubles in LDS)
-template <class Wv>
-DSQ_HD void wide_chol_solve(const WideWork& W, const double* L, double* b) {
+template <class Wv, int MP>
+DSQ_HD void wide_chol_solve(const WideWorkT<MP>& W, const double* L, double* b) {
     const int P = W.P, ld = W.ld;
     for (int i = 0; i < P; ++i) {  // forward, column oriented
         Wv::sync();
@@ -103,8 +124,8 @@ DSQ_HD void wide_chol_solve(const WideWork& W, const double* L, double* b) {
 }
 
 // inv = (L L^T)^-1 (full symmetric), Li = L^-1 as scratch
-template <class Wv>
-DSQ_HD void wide_inverse(const WideWork& W, const double* L, double* Li, double* inv) {
+template <class Wv, int MP>
+DSQ_HD void wide_inverse(const WideWorkT<MP>& W, const double* L, double* Li, double* inv) {
     const int P = W.P, ld = W.ld;
     for (int j = Wv::lane(); j < P; j += Wv::W) {  // column j of L^-1
         Li[j * ld + j] = 1.0 / L[j * ld + j];
@@ -127,8 +148,8 @@ DSQ_HD void wide_inverse(const WideWork& W, const double* L, double* Li, double*
 }
 
 // sum_ij A_ij B_ij over the full symmetric matrices
-template <class Wv>
-DSQ_HD double wide_frob(const WideWork& W, const double* A, const double* B) {
+template <class Wv, int MP>
+DSQ_HD double wide_frob(const WideWorkT<MP>& W, const double* A, const double* B) {
     const int P = W.P, ld = W.ld;
     double s = 0.0;
     for (int i = Wv::lane(); i < P; i += Wv::W) {
@@ -140,7 +161,8 @@ DSQ_HD double wide_frob(const WideWork& W, const double* A, const double* B) {
 }
 
 // q = x^T A x for the column `col` of the staged chunk xs (x_j = xs[j][col])
-DSQ_HD double wide_quad_xs(const WideWork& W, const double* A, int col) {
+template <int MP>
+DSQ_HD double wide_quad_xs(const WideWorkT<MP>& W, const double* A, int col) {
     const int P = W.P, ld = W.ld;
     double s = 0.0;
     for (int i = 0; i < P; ++i) {
@@ -153,22 +175,22 @@ DSQ_HD double wide_quad_xs(const WideWork& W, const double* A, int col) {
 
 // ------------------------------------------------------------------ Gram matrices
 // stage the design chunk of samples n0 .. n0+63 (zeros beyond N) into xs[j][lane]
-template <class Wv>
-DSQ_HD void wide_stage_x(const WideWork& W, const double* Xt, int ldx, int N, int n0) {
+template <class Wv, int MP>
+DSQ_HD void wide_stage_x(const WideWorkT<MP>& W, const double* Xt, int ldx, int N, int n0) {
     for (int l = Wv::lane(); l < 64; l += Wv::W) {
         const int n = n0 + l;
         for (int j = 0; j < W.P; ++j) W.xs[j * kWideXsLd + l] = n < N ? Xt[j * ldx + n] : 0.0;
     }
 }
-template <class Wv>
-DSQ_HD void wide_zero_pad_rows(const WideWork& W) {
+template <class Wv, int MP>
+DSQ_HD void wide_zero_pad_rows(const WideWorkT<MP>& W) {
     for (int l = Wv::lane(); l < 64; l += Wv::W)
         for (int j = W.P; j < W.rows; ++j) W.xs[j * kWideXsLd + l] = 0.0;
 }
 
 // Accumulator of X^T diag(w0) X (and, TWO, X^T diag(w1) X) over chunks; w0 / w1 of the current chunk are W.w[0..63]
 // / W.w[64..127].  Device: MFMA fragments in registers; host: plain sums straight into W.M / W.dM.
-template <class Wv, bool TWO>
+template <class Wv, bool TWO, int MP = kWideMaxP>
 struct WideGram {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef double d4 __attribute__((ext_vector_type(4)));
@@ -176,9 +198,18 @@ struct WideGram {
     // (P <= 8 and TWO: only f0[0], stacked)
     static constexpr int kTiles = 6;
     d4 f0[kTiles], f1[kTiles];
+    // MP > kWideMaxP: up to MP / 16 blocks of rows, (MP / 16)(MP / 16 + 1) / 2 tiles per matrix - too many fragments
+    // for registers.  Tile by tile instead: a lane's fragment of a tile is loaded from W.gacc (its own 4 doubles),
+    // takes the chunk's 16 k-steps and goes back; every entry still sums its samples in order.
+    static constexpr int kMemTiles = (MP / 16) * (MP / 16 + 1) / 2;
+    bool started;
 #endif
-    DSQ_HD void begin(const WideWork& W) {
+    DSQ_HD void begin(const WideWorkT<MP>& W) {
 #if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (MP > kWideMaxP) {
+            started = false;
+            return;
+        }
 #pragma unroll
         for (int t = 0; t < kTiles; ++t) { f0[t] = d4{0.0, 0.0, 0.0, 0.0}; f1[t] = d4{0.0, 0.0, 0.0, 0.0}; }
 #else
@@ -186,9 +217,34 @@ struct WideGram {
 #endif
     }
     // the chunk's xs and w must be in LDS (Wv::sync() by the caller before and after)
-    DSQ_HD void add_chunk(const WideWork& W) {
+    DSQ_HD void add_chunk(const WideWorkT<MP>& W) {
 #if defined(__HIP_DEVICE_COMPILE__)
         const int lane = threadIdx.x & 63, r = lane & 15, kq = lane >> 4;
+        if constexpr (MP > kWideMaxP) {
+            const int nt = W.rows / 16;
+            d4* g0 = (d4*)W.gacc + lane;
+            d4* g1 = g0 + kMemTiles * 64;
+            int ti = 0, tj = 0;
+            for (int t = 0; t < nt * (nt + 1) / 2; ++t) {
+                const d4 z{0.0, 0.0, 0.0, 0.0};
+                d4 a0 = started ? g0[t * 64] : z, a1 = z;
+                if (TWO) a1 = started ? g1[t * 64] : z;
+                const double* xi = W.xs + (16 * ti + r) * kWideXsLd;
+                const double* xj = W.xs + (16 * tj + r) * kWideXsLd;
+#pragma unroll 4
+                for (int s = 0; s < 16; ++s) {
+                    const int n = 4 * s + kq;
+                    const double a = xi[n], b = xj[n];
+                    a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a * W.w[n], b, a0, 0, 0, 0);
+                    if (TWO) a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a * W.w[64 + n], b, a1, 0, 0, 0);
+                }
+                g0[t * 64] = a0;
+                if (TWO) g1[t * 64] = a1;
+                if (++tj > ti) { ++ti; tj = 0; }
+            }
+            started = true;
+            return;
+        }
         const bool stacked = TWO && W.P <= 8;
         const int nt = W.rows / 16;
 #pragma unroll 4
@@ -243,12 +299,32 @@ struct WideGram {
 #endif
     }
     // write the (symmetric) results to W.M (and W.dM)
-    DSQ_HD void finish(const WideWork& W) {
+    DSQ_HD void finish(const WideWorkT<MP>& W) {
         const int P = W.P, ld = W.ld;
 #if defined(__HIP_DEVICE_COMPILE__)
         const int lane = threadIdx.x & 63, col = lane & 15, rq = lane >> 4;
         const bool stacked = TWO && P <= 8;
-        if (stacked) {
+        if constexpr (MP > kWideMaxP) {
+            const int nt = W.rows / 16;
+            const d4* g0 = (const d4*)W.gacc + lane;
+            const d4* g1 = g0 + kMemTiles * 64;
+            int ti = 0, tj = 0;
+            for (int t = 0; t < nt * (nt + 1) / 2; ++t) {
+                const d4 a0 = g0[t * 64];
+                d4 a1 = a0;
+                if (TWO) a1 = g1[t * 64];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int i = 16 * ti + rq + 4 * q, j = 16 * tj + col;
+                    if (i < P && j <= i) {
+                        W.M[i * ld + j] = a0[q];
+                        W.M[j * ld + i] = a0[q];
+                        if (TWO) { W.dM[i * ld + j] = a1[q]; W.dM[j * ld + i] = a1[q]; }
+                    }
+                }
+                if (++tj > ti) { ++ti; tj = 0; }
+            }
+        } else if (stacked) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int row = rq + 4 * q;  // 0..15: rows 0..7 -> M, 8..15 -> dM
@@ -288,8 +364,8 @@ struct WideGram {
 };
 
 // X^T diag(.) X from per-cell sums (cell designs): entry-parallel, both triangles
-template <class Wv>
-DSQ_HD void wide_gram_from_cells(const WideWork& W, const CellDesign& D, const double* cell_sum, double* Mout) {
+template <class Wv, int MP>
+DSQ_HD void wide_gram_from_cells(const WideWorkT<MP>& W, const CellDesign& D, const double* cell_sum, double* Mout) {
     const int P = W.P, ld = W.ld;
     for (int e = Wv::lane(); e < P * P; e += Wv::W) {
         const int i = e / P, j = e % P;
@@ -312,8 +388,8 @@ struct WideAlphaArgs {
 };
 
 // loss / gradient of fit_alpha_mle at log_alpha (same formulas as alpha_eval, dsq_alpha.h)
-template <class Wv, bool GRAD>
-DSQ_HD void alpha_eval_wide(const WideAlphaArgs& A, const WideWork& W, double la, bool cr_reg, bool prior_reg,
+template <class Wv, bool GRAD, int MP>
+DSQ_HD void alpha_eval_wide(const WideAlphaArgs& A, const WideWorkT<MP>& W, double la, bool cr_reg, bool prior_reg,
                             double& f, double& g) {
     la = Wv::uniform(la);
     const double alpha = Wv::uniform(exp(la));
@@ -326,7 +402,7 @@ DSQ_HD void alpha_eval_wide(const WideAlphaArgs& A, const WideWork& W, double la
     const bool cell = A.cells != nullptr;
     KSum accf;
     double accg = 0.0;
-    WideGram<Wv, GRAD> gram;
+    WideGram<Wv, GRAD, MP> gram;
     if (cr_reg) {
         if (cell) {
             for (int c = Wv::lane(); c < kMaxCells; c += Wv::W) { W.acc[c] = 0.0; W.acc[kMaxCells + c] = 0.0; }
@@ -400,9 +476,9 @@ DSQ_HD void alpha_eval_wide(const WideAlphaArgs& A, const WideWork& W, double la
 }
 
 // fit_alpha_mle (utils.py:441-564) incl. the grid-search fallback (grid_search.py:54-142), any P
-template <class Wv>
+template <class Wv, int MP>
 DSQ_HD AlphaOut fit_alpha_wide(const int32_t* y, const double* mu, const double* Xt, int ldx, int N,
-                               const WideWork& W, const CellDesign* cells, double alpha_hat, double min_disp,
+                               const WideWorkT<MP>& W, const CellDesign* cells, double alpha_hat, double min_disp,
                                double max_disp, double prior_var, bool cr_reg, bool prior_reg, Lbfgsb1d& m,
                                const double* cst_in, double* cst_out) {
     WideAlphaArgs A;
@@ -447,15 +523,16 @@ DSQ_HD AlphaOut fit_alpha_wide(const int32_t* y, const double* mu, const double*
 
 // ------------------------------------------------------------------ IRLS (utils.py:273-438) with the fused epilogue
 // vec slots: 0 beta, 1 rhs / solution, 2 beta_init, 3 contrast work, 4 M Hc
-template <class Wv>
-DSQ_HD void irls_sweep_wide(const IrlsArgs& A, const WideWork& W, double a, double& S) {
+template <class Wv, int MP>
+DSQ_HD void irls_sweep_wide(const IrlsArgs& A, const WideWorkT<MP>& W, double a, double& S) {
     // on entry beta = W.v(0); on exit W.M = X^T W X, W.v(1) = X^T W z, S = sum of the deviance terms
     const int P = W.P;
     const bool cell = A.cells != nullptr;
     const double lmin = log(A.min_mu);
     double s = 0.0;
-    WideGram<Wv, false> gram;
-    double rpart = 0.0;  // lane j < P: r_j
+    WideGram<Wv, false, MP> gram;
+    double rpart = 0.0;   // lane j < P: r_j
+    double rpart2 = 0.0;  // MP > 64: lane j < P - 64: r_{j + 64}
     if (cell) {
         const CellDesign& D = *A.cells;
         for (int c = Wv::lane(); c < kMaxCells; c += Wv::W) {
@@ -524,6 +601,8 @@ DSQ_HD void irls_sweep_wide(const IrlsArgs& A, const WideWork& W, double a, doub
             const int j = threadIdx.x & 63;
             if (j < P)
                 for (int n = 0; n < 64; ++n) rpart += W.xs[j * kWideXsLd + n] * W.w[64 + n];
+            if (MP > 64 && j + 64 < P)
+                for (int n = 0; n < 64; ++n) rpart2 += W.xs[(j + 64) * kWideXsLd + n] * W.w[64 + n];
 #else
             for (int j = 0; j < P; ++j)
                 for (int n = 0; n < 64; ++n) W.v(1)[j] += W.xs[j * kWideXsLd + n] * W.w[64 + n];
@@ -545,6 +624,7 @@ DSQ_HD void irls_sweep_wide(const IrlsArgs& A, const WideWork& W, double a, doub
         gram.finish(W);
 #if defined(__HIP_DEVICE_COMPILE__)
         if ((int)(threadIdx.x & 63) < P) W.v(1)[threadIdx.x & 63] = rpart;
+        if (MP > 64 && (int)(threadIdx.x & 63) + 64 < P) W.v(1)[(threadIdx.x & 63) + 64] = rpart2;
 #endif
         Wv::sync();
     }
@@ -552,8 +632,8 @@ DSQ_HD void irls_sweep_wide(const IrlsArgs& A, const WideWork& W, double a, doub
 }
 
 // Wald statistic from W.M = X^T W X at the unclamped mu (no ridge), beta = W.v(0)   (utils.py:718-811)
-template <class Wv>
-DSQ_HD WaldOut wald_wide(const WideWork& W, const double* ridge, const double* contrast, double lfc_null, int alt) {
+template <class Wv, int MP>
+DSQ_HD WaldOut wald_wide(const WideWorkT<MP>& W, const double* ridge, const double* contrast, double lfc_null, int alt) {
     const int P = W.P, ld = W.ld;
     // Hm = M + ridge in W.dM, chol -> W.L, Hc = solve(Hm, c) in v(3), MHc = M Hc in v(4)
     for (int e = Wv::lane(); e < P * P; e += Wv::W) {
@@ -609,8 +689,8 @@ DSQ_HD WaldOut wald_wide(const WideWork& W, const double* ridge, const double* c
 
 // hat diagonal, unclamped mu, fused Cook's bookkeeping and Wald statistics; on entry W.M = X^T W X at the final
 // clamped mu and beta = W.v(0)
-template <class Wv>
-DSQ_HD void irls_finish_wide(const IrlsArgs& A, const WideWork& W, double* mu_out, double* H_out, LfcEpilogue* E) {
+template <class Wv, int MP>
+DSQ_HD void irls_finish_wide(const IrlsArgs& A, const WideWorkT<MP>& W, double* mu_out, double* H_out, LfcEpilogue* E) {
     const int P = W.P;
     const bool want_cooks = E != nullptr && E->flags != nullptr;
     const bool want_wald = E != nullptr && E->ridge != nullptr;
@@ -622,7 +702,7 @@ DSQ_HD void irls_finish_wide(const IrlsArgs& A, const WideWork& W, double* mu_ou
         wide_inverse<Wv>(W, W.L, W.Li, W.inv);
     }
     CooksAcc<Wv> acc(want_cooks ? E->robust_disp : 0.0, want_cooks ? E->cutoff : 0.0, P);
-    WideGram<Wv, false> gram;
+    WideGram<Wv, false, MP> gram;
     if (cell) {
         const CellDesign& D = *A.cells;
         for (int c = Wv::lane(); c < kMaxCells; c += Wv::W) {
@@ -706,8 +786,8 @@ DSQ_HD void irls_finish_wide(const IrlsArgs& A, const WideWork& W, double* mu_ou
 
 // irls_solver (utils.py:273-438) for any P; beta ends in W.v(0).  out.fallback = 1: IRLS diverged, call
 // irls_rescue_wide (nothing has been written).
-template <class Wv>
-DSQ_HD IrlsOut irls_gene_wide(const IrlsArgs& A, const WideWork& W, double* mu_out, double* H_out, LfcEpilogue* E) {
+template <class Wv, int MP>
+DSQ_HD IrlsOut irls_gene_wide(const IrlsArgs& A, const WideWorkT<MP>& W, double* mu_out, double* H_out, LfcEpilogue* E) {
     const int P = W.P;
     IrlsOut out;
     out.converged = 1; out.iters = 0; out.fallback = 0;
@@ -757,8 +837,8 @@ DSQ_HD IrlsOut irls_gene_wide(const IrlsArgs& A, const WideWork& W, double* mu_o
 }
 
 // rescue of a diverged gene (utils.py:374-413): bounded L-BFGS-B from beta_init = W.v(2)
-template <class Wv>
-DSQ_HD IrlsOut irls_rescue_wide(const IrlsArgs& A, const WideWork& W, LbfgsbWork<kWideMaxP>& Lb, double* xlu /*[3][32]*/,
+template <class Wv, int MP>
+DSQ_HD IrlsOut irls_rescue_wide(const IrlsArgs& A, const WideWorkT<MP>& W, LbfgsbWork<MP>& Lb, double* xlu /*[3][MP]*/,
                                 int* nbd, double* mu_out, double* H_out, LfcEpilogue* E) {
     const int P = W.P;
     IrlsOut out;
@@ -772,8 +852,8 @@ DSQ_HD IrlsOut irls_rescue_wide(const IrlsArgs& A, const WideWork& W, LbfgsbWork
     const double cst = Wv::sum(c) - A.N * lgamma_pos(a);
     const double nlogterm = A.N * a * log(A.disp);
     double* x = xlu;
-    double* lo = xlu + kWideMaxP;
-    double* hi = xlu + 2 * kWideMaxP;
+    double* lo = xlu + MP;
+    double* hi = xlu + 2 * MP;
     Wv::sync();
     for (int j = Wv::lane(); j < P; j += Wv::W) { x[j] = W.v(2)[j]; lo[j] = A.min_beta; hi[j] = A.max_beta; nbd[j] = 2; }
     Wv::sync();
@@ -798,7 +878,7 @@ DSQ_HD IrlsOut irls_rescue_wide(const IrlsArgs& A, const WideWork& W, LbfgsbWork
         for (int j = 0; j < P; ++j) pen += 1e-6 * (xb[j] * xb[j]);
         f = (nlogterm - cst + s) + 0.5 * pen;
     };
-    const LbfgsbResult res = lbfgsb_nd<kWideMaxP>(fg, P, x, lo, hi, nbd, Lb);
+    const LbfgsbResult res = lbfgsb_nd<MP>(fg, P, x, lo, hi, nbd, Lb);
     Wv::sync();
     for (int j = Wv::lane(); j < P; j += Wv::W) W.v(0)[j] = x[j];
     Wv::sync();
@@ -813,9 +893,9 @@ DSQ_HD IrlsOut irls_rescue_wide(const IrlsArgs& A, const WideWork& W, LbfgsbWork
 // ------------------------------------------------------------------ the cheap stages at any P
 // rough + moments dispersions, normalised mean and (optionally) the linear-model mu_hat (mom_gene / lin_mu_gene);
 // OLS coefficients in W.v(0)
-template <class Wv>
+template <class Wv, int MP>
 DSQ_HD MomOut mom_wide(const int32_t* y, const double* sf, const double* Xt, const double* pinvXt, int ldx, int N,
-                       const WideWork& W, double s_mean_inv, double min_disp, double max_disp, double min_mu,
+                       const WideWorkT<MP>& W, double s_mean_inv, double min_disp, double max_disp, double min_mu,
                        double* mu_out) {
     const int P = W.P;
     double s = 0.0;
@@ -859,12 +939,12 @@ DSQ_HD MomOut mom_wide(const int32_t* y, const double* sf, const double* Xt, con
 
 // wald_test on given coefficients (Inference.wald_test / another contrast): M from the caller's mu row or from
 // mu = sf exp(X beta); beta must be in W.v(0)
-template <class Wv>
+template <class Wv, int MP>
 DSQ_HD WaldOut wald_gene_wide(const double* mu, const double* sf, const double* Xt, int ldx, int N, double disp,
-                              const WideWork& W, const double* ridge, const double* contrast, double lfc_null,
+                              const WideWorkT<MP>& W, const double* ridge, const double* contrast, double lfc_null,
                               int alt) {
     const int P = W.P;
-    WideGram<Wv, false> gram;
+    WideGram<Wv, false, MP> gram;
     gram.begin(W);
     wide_zero_pad_rows<Wv>(W);
     Wv::sync();
