@@ -1,6 +1,10 @@
 """bench.py — genes/sec of the end-to-end deseq2() hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it generates the matrix, uploads it, warms up, times
+the K steps, writes the outputs if asked to and prints the result line.  `--full` adds every other measurement and
+check, each of which takes runs of its own (listed under "Prints" below); the figures of those are null in a plain line.
 
 A "step" is one pass of the whole path (size factors -> MoM -> mu_hat -> genewise alpha ->
 trend/prior -> MAP alpha -> IRLS LFC -> Cook's (+ refit) -> Wald) over one synthetic count
@@ -18,17 +22,23 @@ DistDeseqPipeline over RCCL (size-factor medians, trend/prior on all-gathered pe
 The harness itself is torch-free: the RCCL unique id travels over a TCP socket
 (pydeseq2_amd.distributed.exchange_unique_id), barriers and the max-over-ranks are RCCL all-gathers.
 
-Prints ONE JSON line on rank 0 (contract in the task brief) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value (genes/s), unit, higher_is_better, dtype, ms_per_step, the workload, and
   roofline     — dominant kernel (dispersion MLE/MAP, k_alpha): algorithmic bytes per launch
                  (12*N bytes per gene: int32 counts + fp64 mu_hat) / mean launch
-                 duration measured with HIP events on the launch stream, vs 8 TB/s HBM peak
+                 duration measured with HIP events on the launch stream IN THE TIMED STEPS, vs 8 TB/s HBM peak
+With `--full` also (options --no-cpu-baseline, --no-extras and --cpu-sample narrow it):
+  kernel_ms_per_step, stage_wall_ms_profiled_step, collective_ms_per_step, evaluations per gene —
+                 one more, untimed step that synchronises and reads HIP events after every stage
   cpu_baseline — the oracle (numpy/scipy restatement of the reference, joblib over host cores)
                  timed on a bounded gene sample of the same workload.
   parity       — the engine re-run on exactly the gene slice the oracle just computed, compared in-run
                  (north-star tolerance 1e-5 on LFC / dispersions / p-values); the speed-up is only
                  reported when it holds.
   h2d_ms / value_with_h2d — the upload of the host count matrix (int64 as the reference holds it) and the
-                 one-off transposition, and the rate that includes them.
+                 one-off transposition, and the rate that includes them (a pipeline is built and closed first, so that
+                 the timed upload does not pay the one-off allocations).
+  summary_tail, lfc_shrink, plugin_path, other_configs, parity_c4 — the summary tail, apeGLM shrinkage, the drop-in path
+                 and the other BASELINE configurations (c2, c4, c5 and one GPU's share of c5) with their own parity objects.
 """
 import argparse
 import json
@@ -538,8 +548,8 @@ class _TimedComm:
 
 def main():
     # A run that hangs (a rendezvous, a device queue) must end with the Python stacks of all threads on stderr and a non-zero
-    # exit code, not sit until the caller's limit: DSQ_BENCH_WATCHDOG_S seconds (default 40 min; the default run takes ~70 s,
-    # the largest configuration on one GPU a few minutes with its generator; 0 disables).
+    # exit code, not sit until the caller's limit: DSQ_BENCH_WATCHDOG_S seconds (default 40 min; a --full run takes about
+    # two minutes, the largest configuration on one GPU a few minutes with its generator; 0 disables).
     import faulthandler
 
     wd = float(os.environ.get("DSQ_BENCH_WATCHDOG_S", "2400"))
@@ -554,15 +564,21 @@ def main():
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="strong (default for --gpus > 1): the configuration's genes are split over the ranks; "
                          "weak: every rank owns the configuration's gene count")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", type=int, default=0)
-    ap.add_argument("--no-extras", action="store_true", help="skip the summary-tail / shrinkage / c4-parity extras")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: upload time, a profiled step, "
+                         "CPU baseline and parity, summary tail, shrinkage, drop-in path, the other configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="with --full: genes of the CPU baseline's sample")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the summary-tail / shrinkage / drop-in / other-configuration extras")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the result of the last timed step as DIR/<field>.npy (float64; per-rank DIR/rank<r>/ "
                          "when --gpus > 1)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: nothing beside the headline figure
+        args.no_cpu_baseline = args.no_extras = True
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(launch_local_ranks(args.gpus, sys.argv[1:]))
@@ -604,13 +620,14 @@ def main():
         control.barrier()
         ctx.sync()
 
-    # ---- upload (host int64 N x G -> HBM, narrowed to int32, + gene-major transposition): timed on its own
-    make_pipe().close()  # first construction pays one-off allocations (pinned staging buffers, code objects)
+    # ---- upload (host int64 N x G -> HBM, narrowed to int32, + gene-major transposition): with --full timed on its own
+    if args.full:
+        make_pipe().close()  # first construction pays one-off allocations (pinned staging buffers, code objects)
     barrier()
     t_up = time.perf_counter()
     pipe = make_pipe()
     ctx.sync()
-    h2d_s = control.max_float(time.perf_counter() - t_up)
+    h2d_s = control.max_float(time.perf_counter() - t_up) if args.full else None
 
     # the very first pass (kernel code objects, pool allocations) and a pass without the previous pass's non-zero mask
     # (what a single deseq2() call on a fresh pipeline pays: the host waits for the mask before it can compact)
@@ -624,7 +641,8 @@ def main():
     ctx.sync()
     first_call_ms = (time.perf_counter() - t_c) * 1e3
     # the W warm-up steps of the steady-state path (the two passes above measure first-call latencies and are not counted:
-    # with W = 2 they used to be the whole warm-up, and the first timed steps still ran 4 % slower than the rest)
+    # with W = 2 they used to be the whole warm-up, and the first timed steps still ran 4 % slower than the rest; a plain
+    # run keeps them too: they load the code objects and fill the pools, so the timed steps start from the same state)
     for _ in range(max(args.warmup, 0)):
         res = pipe.deseq2()
     # The timed region runs the production path (no per-stage synchronisation).  The dispersion
@@ -664,15 +682,16 @@ def main():
     if counting is not None:
         pipe.comm = comm
     klog_timed = pipe.kernel_log
-    # one extra, untimed step with per-stage event timing (synchronises after every stage)
-    coll_log = []
-    if comm is not None:
-        pipe.comm = _TimedComm(comm, ctx, coll_log)
-    pipe.time_kernels, pipe.collect_nfev, pipe.kernel_log = True, True, {}
-    res_prof = pipe.deseq2(profile=True)
-    klog_prof, pipe.time_kernels, pipe.collect_nfev = pipe.kernel_log, False, False
-    if comm is not None:
-        pipe.comm = comm
+    # --full: one extra, untimed step with per-stage event timing (synchronises after every stage)
+    coll_log, klog_prof, res_prof = [], {}, None
+    if args.full:
+        if comm is not None:
+            pipe.comm = _TimedComm(comm, ctx, coll_log)
+        pipe.time_kernels, pipe.collect_nfev, pipe.kernel_log = True, True, {}
+        res_prof = pipe.deseq2(profile=True)
+        klog_prof, pipe.time_kernels, pipe.collect_nfev = pipe.kernel_log, False, False
+        if comm is not None:
+            pipe.comm = comm
     # extras outside `value` (a failure here must not cost the bench line): summary tail (SURVEY 8(f)-1:
     # Cook's filter, independent filtering + BH) and apeGLM LFC shrinkage of the tested coefficient (8(f)-2)
     extras = {}
@@ -766,7 +785,7 @@ def main():
                         "rocprofv3 does",
         "avg_launch_ms_all": round(float(np.mean([ms for ms, _ in launches])), 4), "launches_timed": len(launches),
         "pipeline_algorithmic_GBps": round(G * 104.0 * N / (dt / args.steps) / 1e9, 2),
-        "kernel_ms_per_step": stage_ms, "grid_fallback_genes_per_step": n_fallback,
+        "kernel_ms_per_step": stage_ms if args.full else None, "grid_fallback_genes_per_step": n_fallback,
         "companion": valu,
     }
     for k in ("traffic", "traffic_source", "traffic_ratio"):
@@ -835,7 +854,7 @@ def main():
     if parity is not None and not parity_ok:
         print("[bench] PARITY CHECK FAILED - no speed-up is reported", file=sys.stderr)
 
-    coll_ms = round(float(sum(ms for _, ms in coll_log)), 3) if comm is not None else None
+    coll_ms = round(float(sum(ms for _, ms in coll_log)), 3) if (comm is not None and args.full) else None
     rccl_nranks = None
     if transport == "rccl":
         try:
@@ -846,7 +865,7 @@ def main():
         "metric": "genes/sec end-to-end deseq2() (size factors->dispersion->IRLS->Wald)",
         "value": round(value, 1), "unit": "genes/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-        "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
         "genes_nonzero": int(genes_full),
         "config": {"workload": f"{args.config}: {G_total} genes x {N} samples in total"
                                + (f" ({G} per GPU, {args.scaling} scaling)" if world > 1 else "")
@@ -861,18 +880,18 @@ def main():
                            "pool allocations; the non-zero mask and the row kernels' gene lists come from the upload); "
                            "first_call_ms: a pass that waits for the non-zero mask on the host before compacting (what "
                            "every first call did in round 2), pools warm",
-        "h2d_ms": round(h2d_s * 1e3, 3),
-        "value_with_h2d": round(G_total / (dt / args.steps + h2d_s), 1),
+        "h2d_ms": round(h2d_s * 1e3, 3) if args.full else None,
+        "value_with_h2d": round(G_total / (dt / args.steps + h2d_s), 1) if args.full else None,
         "h2d_note": f"host int64 {N} x {G} ({counts.nbytes / 1e6:.0f} MB per GPU) -> int32 in HBM through pinned "
                     "staging chunks + gene-major transposition; value_with_h2d = genes / (one upload + one step)",
         "collective_ms_per_step": coll_ms,
         "collectives_per_step": (counting.n / max(args.steps, 1)) if counting is not None else None,
-        "collectives_profiled_step": len(coll_log) if comm is not None else None,
+        "collectives_profiled_step": len(coll_log) if (comm is not None and args.full) else None,
         "host_syncs_per_step": round(host_syncs_per_step, 2),
         "roofline": roofline,
         "cpu_baseline": cpu,
         "parity": parity,
-        "stage_wall_ms_profiled_step": {k: round(v * 1e3, 3) for k, v in res_prof.timings.items()},
+        "stage_wall_ms_profiled_step": {k: round(v * 1e3, 3) for k, v in res_prof.timings.items()} if args.full else None,
         "dumped_outputs": dumped,
         "speedup_vs_cpu_baseline": round(value / cpu["value"], 1) if (cpu and parity_ok) else None,
         "speedup_note": "value / cpu_baseline.value: GPU resident rate over the oracle ('port') on this box's host cores; the "

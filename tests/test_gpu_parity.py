@@ -944,7 +944,7 @@ def test_bench_two_ranks_strong_scaling_on_one_gpu():
     """bench.py's multi-GPU path end to end on a one-GPU box: two ranks started by its own launcher share device 0
     (DSQ_BENCH_SHARE_GPU; RCCL refuses two ranks per device, so the collectives take the host-staged transport), strong
     scaling (the named matrix split by genes, sample blocks for the two-collective size factors), one JSON line with
-    the collective timings, and the in-run parity of rank 0's shard against the oracle."""
+    the collective timings, and the in-run parity of rank 0's shard against the oracle (both measured with `--full` only)."""
     import json
     import os
     import subprocess
@@ -955,7 +955,7 @@ def test_bench_two_ranks_strong_scaling_on_one_gpu():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "c2", "--genes",
-                          "3000", "--steps", "2", "--warmup", "2", "--cpu-sample", "600", "--no-extras"],
+                          "3000", "--steps", "2", "--warmup", "2", "--full", "--cpu-sample", "600", "--no-extras"],
                          env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -964,6 +964,40 @@ def test_bench_two_ranks_strong_scaling_on_one_gpu():
     assert d["config"]["genes_per_gpu"] == 1500 and "host-staged" in d["config"]["collectives"]
     assert d["collectives_per_step"] == 3 and d["collective_ms_per_step"] > 0
     assert d["parity"]["ok"], d["parity"]
+
+
+def test_bench_plain_run_measures_the_headline_figure_only(tmp_path):
+    """Without `--full` bench.py times its steps and nothing else: the line carries the headline figure, the workload and the
+    roofline of the dispersion launches timed inside those steps; every figure that takes a run of its own (upload time,
+    profiled step, CPU baseline, parity, extras, other configurations) is null or absent, and `--no-cpu-baseline` /
+    `--no-extras` change nothing.  `--dump-outputs` still writes the last timed step's arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    lines = []
+    for extra in ([], ["--no-cpu-baseline", "--no-extras"]):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "c2", "--genes", "3000", "--steps", "3",
+               "--warmup", "1", "--dump-outputs", str(tmp_path / f"dump{len(lines)}")] + extra
+        out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]))
+    for d in lines:
+        assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+        assert d["unit"] == "genes/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(3000 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+        assert d["roofline"]["full_launch_ms"] > 0 and d["roofline"]["full_launches_timed"] == 2 * 3
+        for k in ("h2d_ms", "value_with_h2d", "cpu_baseline", "parity", "speedup_vs_cpu_baseline",
+                  "stage_wall_ms_profiled_step", "collective_ms_per_step"):
+            assert d[k] is None, k
+        assert d["roofline"]["kernel_ms_per_step"] is None
+        assert not {"summary_tail", "lfc_shrink", "plugin_path", "other_configs", "parity_c4"} & set(d)
+        assert "pvalue" in d["dumped_outputs"]["arrays"]
+        assert np.load(os.path.join(d["dumped_outputs"]["dir"], "pvalue.npy")).shape == (3000,)
+    assert sorted(lines[0]) == sorted(lines[1])
 
 
 @pytest.mark.parametrize("config,genes,per_rank,block", [("c3", 0, 15000, 250), ("c5", 6000, 1500, 1250)])

@@ -7,7 +7,7 @@ for V in "$@"; do
   for CFG in $CFGS; do
     EXTRA=""; [ "$CFG" = "c5" ] && EXTRA="--genes 7500"
     LIB=$REPO/pydeseq2_amd/libdeseq_hip.so; [ "$V" != "main" ] && LIB=$REPO/build/libdeseq_hip_$V.so
-    DSQ_LIB=$LIB timeout 300 python bench.py --config $CFG $EXTRA --steps 8 --warmup 2 --no-cpu-baseline --no-extras > "$OUT/${V}_$CFG.log" 2> "$OUT/${V}_$CFG.err"
+    DSQ_LIB=$LIB timeout 300 python bench.py --config $CFG $EXTRA --steps 8 --warmup 2 --full --no-cpu-baseline --no-extras > "$OUT/${V}_$CFG.log" 2> "$OUT/${V}_$CFG.err"
     python - "$OUT/${V}_$CFG.log" "$V $CFG" <<'PY'
 import json, sys
 try:

@@ -6,7 +6,7 @@ for rep in 1 2; do
   i=0
   for lib in "$@"; do
     i=$((i+1))
-    DSQ_LIB=$lib timeout 900 python bench.py $ARGS --no-extras --no-cpu-baseline > $OUT/lib_${i}_$rep.log 2> $OUT/lib_${i}_$rep.err
+    DSQ_LIB=$lib timeout 900 python bench.py $ARGS --full --no-extras --no-cpu-baseline > $OUT/lib_${i}_$rep.log 2> $OUT/lib_${i}_$rep.err
     python - "$OUT/lib_${i}_$rep.log" "$lib" <<'PY'
 import json, sys
 try:

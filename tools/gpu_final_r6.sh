@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 6: everything committed under profiles/r06_* from ONE call: kernel stats + FETCH / WRITE per configuration, timelines / idle
-# gaps, SQ counters, the fp64 instruction mix (flops_*.json), stage-by-stage parity, the drop-in path, the default bench line
+# gaps, SQ counters, the fp64 instruction mix (flops_*.json), stage-by-stage parity, the drop-in path, the bench line of a --full run
 set -u
 export TMPDIR=/tmp
 mkdir -p gpurun_out/r06
@@ -15,4 +15,5 @@ for c in c2 c3 c4; do bash tools/pmc_flops.sh r06_fl $c > /dev/null 2>&1; done; 
 for a in "c2 2000" "c2 20000" "c3 8000"; do set -- $a; python tests/tools/stage_diff.py $1 $2 > gpurun_out/r06/stage_diff_$1_$2.json 2> gpurun_out/r06/stage_diff_$1_$2.err; done; echo stage diff done
 python tools/probes/plugin_probe.py c3 > gpurun_out/r06/plugin_c3.json 2> gpurun_out/r06/plugin_c3.err; tail -c 300 gpurun_out/r06/plugin_c3.json; echo
 python tools/probes/plugin_probe.py c4 > gpurun_out/r06/plugin_c4.json 2> gpurun_out/r06/plugin_c4.err; tail -c 200 gpurun_out/r06/plugin_c4.json; echo
-( time python bench.py ) > gpurun_out/r06/bench_default.json 2> gpurun_out/r06/bench_default.err; tail -4 gpurun_out/r06/bench_default.err
+OUT=$(ls -d */r06)  # the directory made above
+( time python bench.py --full ) > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; tail -4 "$OUT/bench_default.err"

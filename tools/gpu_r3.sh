@@ -13,7 +13,7 @@ grep -E "^FAILED|^ERROR" "$OUT/pytest.log" | cut -c1-300
 cp gpurun_out/parity_vs_reference_*.json "$OUT/" 2>/dev/null
 fi
 run() { # name, env, args
-  env $2 timeout 900 python bench.py $3 > "$OUT/$1.log" 2> "$OUT/$1.err"
+  env $2 timeout 900 python bench.py --full $3 > "$OUT/$1.log" 2> "$OUT/$1.err"
   echo "== $1"; python - "$OUT/$1.log" <<'PY'
 import json, sys
 try:

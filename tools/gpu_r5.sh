@@ -13,7 +13,7 @@ else
 shift
 fi
 shift
-( time timeout 1500 python bench.py "$@" ) > "$OUT/bench.log" 2> "$OUT/bench.err"
+( time timeout 1500 python bench.py --full "$@" ) > "$OUT/bench.log" 2> "$OUT/bench.err"
 tail -4 "$OUT/bench.err"
 python - "$OUT/bench.log" <<'PY'
 import json, sys

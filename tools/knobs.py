@@ -65,7 +65,7 @@ KNOBS = {
     "DSQ_BENCH_WATCHDOG_S": ("bench", "2400", "seconds after which a bench run that is still going dumps its Python stacks and exits non-zero (0: off)"),
     "DSQ_FORCE_DIST": ("bench", "off", "take the distributed pipeline with one rank"),
     "DSQ_BENCH_NO_PLUGIN": ("bench", "off", "skip the drop-in-path measurement"),
-    "DSQ_BENCH_NO_C5_FULL": ("bench", "off", "skip the full-size c5 measurement of the default run"),
+    "DSQ_BENCH_NO_C5_FULL": ("bench", "off", "skip the full-size c5 measurement of a --full run"),
 }
 BEGIN, END = "<!-- knobs:begin (generated by tools/knobs.py) -->", "<!-- knobs:end -->"
 

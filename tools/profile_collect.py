@@ -17,7 +17,7 @@ def main():
     src = os.path.join(ROOT, "gpurun_out", tag)
     bench = [l for l in open(os.path.join(src, "bench_prof.log")) if l.startswith("{")][-1].strip()
     extra_args = os.environ.get("PROFILE_BENCH_ARGS", "")
-    out = [f"# {tag} — rocprofv3 --kernel-trace --stats -- python bench.py --config {cfg} --steps 5 --warmup 2 --no-extras"
+    out = [f"# {tag} — rocprofv3 --kernel-trace --stats -- python bench.py --config {cfg} --steps 5 --warmup 2 --full --no-extras"
            f"{(' ' + extra_args) if extra_args else ''}  (MI355X)",
            "# bench line of the same (profiled) run:", bench, "", open(os.path.join(src, "stats.txt")).read(),
            "# separate PMC passes (rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE; 1 step, no warmup).",
