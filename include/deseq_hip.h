@@ -473,6 +473,17 @@ int dsq_dev_wald(dsq_ctx* ctx, const double* d_mu, int ldn, const double* d_sf, 
                  int ldx, int N, int G, int P, const double* d_disp, const double* d_beta,
                  const double* h_ridge, const double* h_contrast, double lfc_null, int alt,
                  double* d_pvals, double* d_stats, double* d_se);
+/* Likelihood-ratio test of a nested reduced design (DESeq2's nbinomLRT; csrc/dsq_lrt.h): per gene
+ *   stat = 2 sum_n [ y (eta_f - eta_r) - (y + 1/disp) (log(1/disp + mu_f) - log(1/disp + mu_r)) ],  mu = sf exp(X beta)
+ * from the coefficients of the two fits (d_beta [G][P], d_beta_reduced [G][P_reduced], both at the dispersions d_disp),
+ * and pvalue = Q((P - P_reduced) / 2, stat / 2) (a negative statistic: 1; NaN dispersion: NaN).  d_Xt_reduced: the
+ * reduced design transposed, [P_reduced][ldx_reduced]; 1 <= P_reduced < P <= DSQ_MAX_P. */
+int dsq_dev_lrt(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, const double* d_Xt, int ldx, int P,
+                const double* d_Xt_reduced, int ldx_reduced, int P_reduced, int N, int G, const double* d_disp,
+                const double* d_beta, const double* d_beta_reduced, double* d_stats, double* d_pvals);
+/* d_out[i] = survival function of the chi-square distribution with df degrees of freedom (an integer, 1 ... 127) at
+ * d_x[i] (scipy.stats.chi2.sf): 1 for x <= 0. */
+int dsq_dev_chisq_sf(dsq_ctx* ctx, const double* d_x, int n, int df, double* d_out);
 /* row gathers for the refit sub-problem: dst[k][:] = src[idx[k]][:] */
 /* O(G) glue that keeps the dispersion vectors device-resident between the stages:
  * fitted trend a0 + a1/normed_mean (dds.py:826-833; a1 == 0: mean trend), final dispersions with the

@@ -21,7 +21,7 @@ from . import summary as _summary
 from ._design import DesignPack
 from . import _lib
 from ._lib import Context
-from .pipeline import DeseqPipeline
+from .pipeline import DeseqPipeline, check_reduced_design
 
 
 def build_design(metadata: pd.DataFrame, design, ref_level=None) -> pd.DataFrame:
@@ -400,6 +400,8 @@ class DeseqDataSet:
             lay.offer("cooks", "_mu_hat")
             if "refitted" in v and np.asarray(r.refitted, bool).any():
                 lay.offer("replace_cooks")
+            if "replaced" in v and np.asarray(r.replaced, bool).any():
+                lay.offer("replace_counts")
         else:  # dds.py:1032-1034
             obm.withdraw("_mu_LFC", "_hat_diagonals")
             lay.withdraw("_mu_LFC", "_hat_diagonals", "_mu_hat")
@@ -616,7 +618,7 @@ class DeseqDataSet:
             self._finish()
         out = pd.Series(np.asarray(self.var["_pvalue_cooks_outlier"], dtype=bool), index=self.var_names)
         if self.low_memory:  # dds.py:1103-1106
-            self.layers.withdraw("cooks", "replace_cooks")
+            self.layers.withdraw("cooks", "replace_cooks", "replace_counts")
         return out
 
     def _ensure_finished(self):
@@ -785,7 +787,7 @@ class _Lazy(dict):
 
 class _LazyLayers(_Lazy):
     """``normed_counts``, ``_mu_hat``, ``_mu_LFC``, ``_hat_diagonals``, ``cooks``, ``replace_cooks``: N x G, NaN columns for
-    the genes without counts."""
+    the genes without counts; ``replace_counts``: the integer counts with the replaced outliers."""
 
     _attr = "layers"
 
@@ -805,6 +807,8 @@ class _LazyLayers(_Lazy):
             for j in np.nonzero(np.asarray(dds.var["refitted"], dtype=bool))[0]:
                 ck[rep, j] = 0.0
             return ck
+        if key == "replace_counts":  # dds.py:1329-1358: the counts with the Cook's outliers of the replaced genes imputed
+            return dds._pipe.layer("replace_counts")
         name = {"_mu_LFC": "mu_LFC", "_hat_diagonals": "hat_diagonals", "cooks": "cooks"}.get(key)
         if name is None:
             raise KeyError(key)
@@ -825,11 +829,50 @@ class _LazyObsm(_Lazy):
         return np.ascontiguousarray(full[:, np.asarray(dds.var["non_zero"], dtype=bool)])
 
 
+def _check_lrt_hypothesis(lfc_null, alt_hypothesis):
+    if lfc_null != 0 or alt_hypothesis is not None:
+        raise ValueError("The likelihood-ratio test has no lfc_null / alt_hypothesis: it compares two nested designs "
+                         "(use test='wald' for a thresholded or one-sided test).")
+
+
+def reduced_design_matrix(dds, reduced) -> pd.DataFrame:
+    """The reduced design of a likelihood-ratio test as a DataFrame over the samples of ``dds``: a formula over its
+    metadata (built like the full design, same ``ref_level``), a DataFrame or a matrix.  Host only.  ValueError when it
+    does not fit the full design (rows, 1 ... P - 1 columns, full rank, nested)."""
+    if isinstance(reduced, str):
+        Xr = build_design(dds.obs, reduced, dds._ref_level)
+    elif isinstance(reduced, pd.DataFrame):
+        Xr = reduced.astype(float)
+    else:
+        a = np.asarray(reduced, dtype=float)
+        if a.ndim != 2:
+            raise ValueError("The reduced design must be a samples x columns matrix.")
+        Xr = pd.DataFrame(a, columns=[f"x{j}" for j in range(a.shape[1])])
+    check_reduced_design(np.asarray(dds.obsm["design_matrix"], dtype=float), Xr.to_numpy())
+    return Xr.set_axis(dds.obs_names, axis=0)
+
+
 class DeseqStats:
-    """Wald tests, adjusted p-values and LFC shrinkage (cf. ``pydeseq2.ds.DeseqStats``, ds.py:110-447)."""
+    """Wald tests, adjusted p-values and LFC shrinkage (cf. ``pydeseq2.ds.DeseqStats``, ds.py:110-447).
+
+    ``test="LRT"`` with ``reduced=`` (a formula over the same metadata such as ``"~batch"`` or ``"~1"``, a matrix or a
+    DataFrame whose columns span a subspace of the full design's) replaces the Wald statistic and p-value by those of
+    the likelihood-ratio test of the reduced design (DESeq2's ``nbinomLRT``); ``log2FoldChange`` / ``lfcSE`` stay those
+    of the contrast, and the p-values pass through the same Cook's filter, independent filtering and BH."""
 
     def __init__(self, dds: DeseqDataSet, contrast, alpha=0.05, cooks_filter=True, independent_filter=True,
-                 prior_LFC_var=None, lfc_null=0.0, alt_hypothesis=None, inference=None, quiet=True, n_cpus=None):
+                 prior_LFC_var=None, lfc_null=0.0, alt_hypothesis=None, inference=None, quiet=True, n_cpus=None, *,
+                 test="wald", reduced=None):
+        if test not in ("wald", "LRT"):
+            raise ValueError(f"test must be 'wald' or 'LRT' (got {test!r}).")
+        self.test, self.reduced_design = test, None
+        if test == "LRT":  # (host-only checks: before anything touches the GPU)
+            if reduced is None:
+                raise ValueError("test='LRT' needs a reduced design: reduced='~batch', '~1', a matrix or a DataFrame.")
+            _check_lrt_hypothesis(lfc_null, alt_hypothesis)
+            self.reduced_design = reduced_design_matrix(dds, reduced)
+        elif reduced is not None:
+            raise ValueError("reduced is the reduced design of the likelihood-ratio test: pass test='LRT' with it.")
         finish = getattr(dds, "_ensure_finished", None)
         if finish is not None:
             finish()  # (a stage-wise pass left open after fit_LFC() / calculate_cooks() is run to its end)
@@ -888,13 +931,35 @@ class DeseqStats:
         if hasattr(self, "padj"):
             del self.padj
 
+    def run_lrt_test(self):
+        """Likelihood-ratio test of ``reduced`` (``DeseqPipeline.lrt``): ``statistics`` / ``p_values`` are the LRT's,
+        ``SE`` stays the contrast's standard error (a Wald quantity); also ``reduced_LFC`` and ``reduced_converged``."""
+        if self.test != "LRT":
+            raise ValueError("run_lrt_test() needs DeseqStats(..., test='LRT', reduced=...).")
+        _check_lrt_hypothesis(self.lfc_null, self.alt_hypothesis)
+        if not hasattr(self, "SE"):
+            self.run_wald_test()
+        pv, st, beta_r, conv = self.dds._pipe.lrt(self.dds._res, self.reduced_design.to_numpy())
+        idx = self.dds.var_names
+        self.p_values, self.statistics = pd.Series(pv, index=idx), pd.Series(st, index=idx)
+        self.reduced_LFC = pd.DataFrame(beta_r, index=idx, columns=self.reduced_design.columns)
+        self.reduced_converged = pd.Series(conv, index=idx)
+        self._wald_key = ("LRT",)
+        if hasattr(self, "padj"):
+            del self.padj
+
     def summary(self, **kwargs) -> pd.DataFrame:
         """Wald test, Cook's filtering, adjusted p-values; returns and stores ``results_df`` (ds.py:219-299).
         The Wald test is (re)run only when there are no p-values yet or ``lfc_null`` / ``alt_hypothesis`` change
-        (ds.py:255-264), so a summary after ``lfc_shrink`` keeps the shrunk coefficients with their standard errors."""
+        (ds.py:255-264), so a summary after ``lfc_shrink`` keeps the shrunk coefficients with their standard errors.
+        With ``test="LRT"`` the statistic and the p-values are the likelihood-ratio test's."""
         self.lfc_null = kwargs.get("lfc_null", self.lfc_null)
         self.alt_hypothesis = kwargs.get("alt_hypothesis", self.alt_hypothesis)
-        if not hasattr(self, "p_values") or getattr(self, "_wald_key", None) != (self.lfc_null, self.alt_hypothesis):
+        if self.test == "LRT":
+            _check_lrt_hypothesis(self.lfc_null, self.alt_hypothesis)
+            if getattr(self, "_wald_key", None) != ("LRT",):
+                self.run_lrt_test()
+        elif not hasattr(self, "p_values") or getattr(self, "_wald_key", None) != (self.lfc_null, self.alt_hypothesis):
             self.run_wald_test()
         if not hasattr(self, "padj"):
             if self.cooks_filter:

@@ -593,6 +593,23 @@ int dsq_dev_wald(dsq_ctx* ctx, const double* d_mu, int ldn, const double* d_sf, 
     return DSQ_OK;
 }
 
+int dsq_dev_lrt(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, const double* d_Xt, int ldx, int P,
+                const double* d_Xt_reduced, int ldx_reduced, int P_reduced, int N, int G, const double* d_disp,
+                const double* d_beta, const double* d_beta_reduced, double* d_stats, double* d_pvals) {
+    DSQ_CHECK_ARG(P >= 2 && P <= DSQ_MAX_P, "P out of range");
+    DSQ_CHECK_ARG(P_reduced >= 1 && P_reduced < P, "P_reduced: between 1 and P - 1 columns");
+    DSQ_CHECK_ARG(ldn >= N && ldx >= N && ldx_reduced >= N, "a leading dimension is smaller than N");
+    DSQ_HIP(dsq::launch_lrt(ctx->stream, d_y, ldn, d_sf, d_Xt, ldx, P, d_Xt_reduced, ldx_reduced, P_reduced, N, G, d_disp,
+                            d_beta, d_beta_reduced, d_stats, d_pvals));
+    return DSQ_OK;
+}
+
+int dsq_dev_chisq_sf(dsq_ctx* ctx, const double* d_x, int n, int df, double* d_out) {
+    DSQ_CHECK_ARG(df >= 1 && df <= DSQ_MAX_P - 1, "df: an integer between 1 and 127");
+    DSQ_HIP(dsq::launch_chisq_sf(ctx->stream, d_x, n, df, d_out));
+    return DSQ_OK;
+}
+
 int dsq_dev_gather_rows_f64(dsq_ctx* ctx, const double* d_src, int ld, const int32_t* d_idx, int n_idx,
                             int ncols, double* d_dst) {
     DSQ_HIP(dsq::launch_gather_rows_f64(ctx->stream, d_src, ld, d_idx, n_idx, ncols, d_dst));

@@ -321,6 +321,12 @@ hipError_t launch_wald(hipStream_t st, const double* mu, int ldn, const double* 
                        int ldx, int N, int G, int P, const double* disp, const double* beta,
                        const double* d_ridge, const double* d_contrast, double lfc_null, int alt,
                        double* pvals, double* stats, double* se);
+// ---- dsq_k_lrt.hip: likelihood-ratio statistic of a reduced design (Xr: its transposed design, 1 <= Pr < Pf) and the
+// chi-square survival function with integer degrees of freedom
+hipError_t launch_lrt(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* Xf, int ldf, int Pf,
+                      const double* Xr, int ldr, int Pr, int N, int G, const double* disp, const double* beta_f,
+                      const double* beta_r, double* stat, double* pval);
+hipError_t launch_chisq_sf(hipStream_t st, const double* x, int n, int df, double* out);
 hipError_t launch_cooks(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* mu,
                         const double* hat, const int32_t* cell_offsets, const int32_t* cell_index,
                         int n_cells, int whole, int max_cell, const uint8_t* flags, int N, int G,

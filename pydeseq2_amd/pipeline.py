@@ -78,6 +78,29 @@ def _trigamma(x):
     return float(polygamma(1, x))
 
 
+def check_reduced_design(X, reduced_design):
+    """The reduced design of a likelihood-ratio test against the full design X, as a float matrix - or a ValueError that
+    names what is wrong with it.  Host only."""
+    X = np.asarray(X, dtype=np.float64)
+    Xr = np.asarray(reduced_design, dtype=np.float64)
+    N, P = X.shape
+    if Xr.ndim != 2:
+        raise ValueError("The reduced design must be a samples x columns matrix.")
+    if Xr.shape[0] != N:
+        raise ValueError(f"The reduced design has {Xr.shape[0]} rows; the data set has {N} samples.")
+    if not 1 <= Xr.shape[1] <= P - 1:
+        raise ValueError(f"The reduced design must have between 1 and {P - 1} columns (fewer than the full design's "
+                         f"{P}); it has {Xr.shape[1]}.")
+    if np.isnan(Xr).any():
+        raise ValueError("NaNs are not allowed in the reduced design.")
+    if np.linalg.matrix_rank(Xr) != Xr.shape[1]:
+        raise ValueError("The reduced design is rank deficient (its columns are linearly dependent).")
+    if np.linalg.matrix_rank(np.hstack([Xr, X])) != np.linalg.matrix_rank(X):
+        raise ValueError("The reduced design is not nested in the full design: its columns must lie in the span of the "
+                         "full design's columns.")
+    return np.ascontiguousarray(Xr)
+
+
 class _Respeculate(Exception):
     """The pass was enqueued on the previous pass's non-zero mask and the matrix has another one: run it again, in order."""
 
@@ -237,6 +260,9 @@ class DeseqPipeline:
         self._inflight = []
         self._side_pending = False
         self._pinned = _PinnedPool(ctx_)
+        # the replaced counts of the last pass's refit (Gr x N int32) in a buffer of their own - the pool recycles its
+        # buffers with the next pass - and where they belong: lrt() fits its reduced design on them, layer("replace_counts")
+        self._replace_buf, self._replace_keep = None, None
         # Which genes have a count at all depends on the counts only: the mask every pass compacts to is computed here, once,
         # so that the first deseq2() call already enqueues its genewise stage without waiting for it (each pass still
         # re-derives the mask on the device and compares), and the gene lists of the row kernels are built off the step.
@@ -613,6 +639,16 @@ class DeseqPipeline:
                 _vp(ridge.ctypes.data), _vp(contrast.ctypes.data), c_double(lfc_null), alt,
                 _vp(S["p"].ptr), _vp(S["stat"].ptr), _vp(S["se"].ptr), _vp(self._mix) if self._mix else None, cooks_ld)
         return d_mu, d_hat
+
+    def _replace_rows(self, Gr):
+        """Gr x N int32 rows (pitch ldn) that outlive the pass: one allocation, grown when a pass replaces more genes than
+        any before it (a steady-state step allocates nothing)."""
+        if self._replace_buf is None or self._replace_buf.shape[0] < Gr:
+            if self._replace_buf is not None:
+                self.ctx.sync()
+                self._replace_buf.free()
+            self._replace_buf = DeviceArray(self.ctx, (int(Gr), self.N), np.int32, ld=self.ldn)
+        return self._replace_buf
 
     def _cooks_ld(self):
         """Row pitch of a slot-ordered Cook's layer (mixed designs the IRLS kernel takes), else 0: sample order, pitch ldn."""
@@ -1120,6 +1156,7 @@ class DeseqPipeline:
         ctx, r, S, Gn, N = self.ctx, st.r, st.S, st.Gn, self.N
         st.replaced_nz = np.zeros(Gn, dtype=bool)
         st.patch = None
+        self._replace_keep = None  # (the kept rows are those of the LAST pass)
         if getattr(st, "force_refit", False) and not st.want_refit and self.design.replaceable.sum() > 0:
             # DeseqDataSet.refit() called by hand on a data set built with refit_cooks=False (dds.py:1042-1064)
             st.want_refit, st.flags_tok = True, self._fetch_begin(S, ["any_all"])
@@ -1130,7 +1167,8 @@ class DeseqPipeline:
             Gr = len(rp)
             if Gr > 0:
                 d_rp = self._up(rp.astype(np.int32), np.int32)
-                d_ysub = self._dmat(Gr, np.int32)
+                d_ysub = self._replace_rows(Gr)
+                self._replace_keep = {"Gr": Gr, "rp": rp, "nzi": st.nzi, "naz": None}
                 S2 = self._dev_slab(Gr)
                 d_az = S2["naz"]  # its own field: no stage of the sub-problem writes it
                 ctx.call("dsq_dev_replace_outliers2", _vp(st.d_ynz.ptr), _vp(st.d_cooks.ptr), self.ldn, _vp(st.d_sf.ptr),
@@ -1182,6 +1220,8 @@ class DeseqPipeline:
         if st.patch is not None:  # dds.py:1368-1458: the refitted genes take their new values
             rp, h2 = st.patch[0], self._fetch_end(st.patch[1])
             naz = h2["naz"].astype(bool)  # all counts zero after the replacement (dds.py:1368-1383)
+            if self._replace_keep is not None:
+                self._replace_keep["naz"] = naz.copy()
             new_zero_nz[rp[naz]] = True
             refitted_nz[rp[~naz]] = True
             rf, k = rp[~naz], np.nonzero(~naz)[0]
@@ -1357,6 +1397,90 @@ class DeseqPipeline:
             se[z], st[z], pv[z] = 0.0, 0.0, 1.0
         return pv, st, se
 
+    # ------------------------------------------------------------------ likelihood-ratio test
+    def lrt(self, res: DeseqResult, reduced_design):
+        """Likelihood-ratio test of a nested reduced design (DESeq2's nbinomLRT) on the dispersions / LFCs of ``res``,
+        post hoc like wald().  The reduced design is fitted by the IRLS launcher of the LFC stage (dsq_dev_lfc_fit2
+        without epilogue, the reduced design's own DesignPack and cells) with the final dispersions, size factors and
+        settings of fit_LFC, on the counts the final LFC was fitted on - the replaced counts of the last pass for the
+        refitted genes - and k_lrt scores the two fits (csrc/dsq_lrt.h).
+        Returns (pvalue, stat, reduced_LFC [G x P_reduced, natural log], reduced_converged); NaN for all-zero genes;
+        genes whose counts all became zero in the refit: stat 0, pvalue 1 (the Wald rule, ds.py:357-360) and reduced_LFC 0."""
+        Xr = check_reduced_design(self.design.X, reduced_design)
+        G, N, ctx = self.G, self.N, self.ctx
+        Dr = DesignPack(Xr, self.min_replicates)
+        Pr = Dr.P
+        nz = np.asarray(res.non_zero, dtype=bool)
+        nzi = np.nonzero(nz)[0]
+        Gn = len(nzi)
+        pv, stt = np.full(G, np.nan), np.full(G, np.nan)
+        beta_r, conv_r = np.full((G, Pr), np.nan), np.full(G, np.nan)
+        refitted = np.asarray(res.refitted, dtype=bool) if res.refitted is not None else np.zeros(G, dtype=bool)
+        keep = self._replace_keep
+        if refitted.any() and (keep is None or keep["naz"] is None):
+            raise RuntimeError("lrt(): the replaced counts of this result's refit are gone (another pass has run since)")
+        held = []  # device arrays of this call
+
+        def dev(a):
+            held.append(DeviceArray.from_host(ctx, np.ascontiguousarray(a)))
+            return held[-1]
+
+        try:
+            d_sf = dev(np.asarray(res.size_factors, dtype=np.float64))
+            d_Xr, d_pinv = dev(Dr.Xt), dev(Dr.pinvXt)
+            cells = None
+            if Dr.cell_path and not os.environ.get("DSQ_NO_CELL_PATH"):
+                cells = DsqCells(dev(Dr.cell_of).ptr, dev(Dr.Xc).ptr, dev(Dr.XXc).ptr, int(Dr.n_design_cells))
+
+            def run(d_y, idx):
+                """Reduced fit + statistic of the rows of d_y, which are the genes idx -> host vectors."""
+                Gs = len(idx)
+                d_bf = dev(np.asarray(res.LFC, dtype=np.float64)[idx])
+                d_disp = dev(np.asarray(res.dispersions, dtype=np.float64)[idx])
+                d_br, d_cv = DeviceArray(ctx, (Gs, Pr), np.float64), DeviceArray(ctx, (Gs,), np.uint8)
+                d_out = DeviceArray(ctx, (2 * Gs,), np.float64)
+                held.extend([d_br, d_cv, d_out])
+                self._k("lrt_reduced_fit", Gs, "dsq_dev_lfc_fit2", _vp(d_y.ptr), self.ldn, _vp(d_sf.ptr), _vp(d_Xr.ptr),
+                        _vp(d_pinv.ptr), Dr.ldx, N, Gs, Pr, int(Dr.full_rank), _vp(d_disp.ptr), c_double(self.min_mu),
+                        c_double(self.beta_tol), c_double(-30.0), c_double(30.0), self.irls_maxiter, _vp(d_br.ptr), None,
+                        None, _vp(d_cv.ptr), None, C.byref(cells) if cells is not None else None,
+                        None, None, c_double(0.0), None, None, None, None, None,
+                        None, None, c_double(0.0), 0, None, None, None, None, 0)
+                self._k("lrt", Gs, "dsq_dev_lrt", _vp(d_y.ptr), self.ldn, _vp(d_sf.ptr), _vp(self.d_Xt.ptr),
+                        self.design.ldx, self.P, _vp(d_Xr.ptr), Dr.ldx, Pr, N, Gs, _vp(d_disp.ptr), _vp(d_bf.ptr),
+                        _vp(d_br.ptr), _vp(d_out.ptr), _vp(d_out.ptr + 8 * Gs))
+                o = d_out.to_host()
+                return o[Gs:], o[:Gs], d_br.to_host(), d_cv.to_host().astype(float)
+
+            if Gn > 0:
+                if Gn == G:
+                    d_y = self.d_y
+                else:
+                    d_idx = dev(nzi.astype(np.int32))
+                    d_y = DeviceArray(ctx, (Gn, N), np.int32, ld=self.ldn)
+                    held.append(d_y)
+                    ctx.call("dsq_dev_gather_rows_i32", _vp(self.d_y.ptr), self.ldn, _vp(d_idx.ptr), Gn, N, _vp(d_y.ptr))
+                pv[nzi], stt[nzi], beta_r[nzi], conv_r[nzi] = run(d_y, nzi)
+            if refitted.any():  # their final LFC was fitted on the replaced counts: so is their reduced model
+                rows = np.nonzero(~keep["naz"])[0]
+                gidx = (keep["rp"] if keep["nzi"] is None else keep["nzi"][keep["rp"]])[rows]
+                if not np.array_equal(np.sort(gidx), np.nonzero(refitted)[0]):
+                    raise RuntimeError("lrt(): the kept replaced counts belong to another result")
+                d_sel = dev(rows.astype(np.int32))
+                d_y2 = DeviceArray(ctx, (len(rows), N), np.int32, ld=self.ldn)
+                held.append(d_y2)
+                ctx.call("dsq_dev_gather_rows_i32", _vp(self._replace_buf.ptr), self.ldn, _vp(d_sel.ptr), len(rows), N,
+                         _vp(d_y2.ptr))
+                pv[gidx], stt[gidx], beta_r[gidx], conv_r[gidx] = run(d_y2, gidx)
+        finally:
+            ctx.sync()
+            for a in held:
+                a.free()
+        z = np.asarray(res.new_all_zeroes, dtype=bool) if res.new_all_zeroes is not None else np.zeros(G, dtype=bool)
+        if z.any():  # ds.py:357-360, dds.py:1380-1383
+            stt[z], pv[z], beta_r[z] = 0.0, 1.0, 0.0
+        return pv, stt, beta_r, conv_r
+
     def close(self):
         """Release the pooled device buffers."""
         if getattr(self, "_side_pending", False) or getattr(self, "_lfc_forked", False):
@@ -1372,6 +1496,9 @@ class DeseqPipeline:
         if getattr(self, "_mix", None):
             self.ctx.lib.dsq_mix_destroy(_vp(self._mix))
             self._mix = None
+        if getattr(self, "_replace_buf", None) is not None:
+            self._replace_buf.free()
+            self._replace_buf, self._replace_keep = None, None
         self._pinned.close()
 
     def __del__(self):
@@ -1382,7 +1509,17 @@ class DeseqPipeline:
 
     # ------------------------------------------------------------------ lazy N x G layers
     def layer(self, name):
-        """Fetch an N x G layer ("mu_LFC", "hat_diagonals", "cooks") to the host (NaN for zero genes)."""
+        """Fetch an N x G layer ("mu_LFC", "hat_diagonals", "cooks") to the host (NaN for zero genes);
+        "replace_counts": the counts with the outliers of the last pass replaced (dds.py:1329-1358; int64, the columns of
+        the genes that became all-zero are zero)."""
+        if name == "replace_counts":
+            out = self.d_raw.to_host().astype(np.int64)
+            k = self._replace_keep
+            if k is not None and k["naz"] is not None:
+                rows = self.ctx.d2h_rows(self._replace_buf.ptr, k["Gr"], self.N, self.ldn, np.int32)
+                rows[k["naz"]] = 0  # (such a row keeps its original counts on the device, csrc k_replace)
+                out[:, k["rp"] if k["nzi"] is None else k["nzi"][k["rp"]]] = rows.T
+            return out
         d = self.layers[name]
         if d is None:  # mu / hat diagonals of the LFC fit were consumed in its epilogue: rebuild from beta
             d_y, d_sf, d_b, d_d, Gn = self.layers["_fit"]
