@@ -1,4 +1,5 @@
-"""ctypes front-end of the TEST-ONLY device build of dsq_math.h / dsq_wave.h (see devunit.hip).
+"""ctypes front-end of the TEST-ONLY device build of dsq_math.h / dsq_wave.h (see devunit.hip) and of dsq_wide.h /
+dsq_wider.h / row_chol_solve (see devunit_linalg.hip).
 
 Every function takes numpy arrays, pads them to whole 256-thread blocks where the caller has not, runs one entry point
 (allocate, copy, launch, synchronise, free) and raises on a non-zero hipError_t."""
@@ -14,6 +15,8 @@ MATH_OPS = ["frcp", "frsq", "frcp_g", "fdiv", "flog", "flog_t", "flog1p", "flog1
             "digamma_pos", "lgdg00", "lgdg10", "lgdg01", "lgdg11", "norm_sf", "stirling_big", "log_count"]
 WAVE_OPS = ["sum", "sumi", "maxi", "max", "excl_scan_i", "from_lane", "uniform", "readlane_d", "row_bcast", "any",
             "hist_add", "slot_add", "slot_add_third", "cell_add"]
+LIN_OPS = ["chol", "logdet", "solve", "inverse", "frob", "quad_xs", "cells"]
+ROW_P = (3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 16)  # k_irls_row's widths, and 16
 SUM_N_K = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 16, 24, 48)
 BLOCK = 256
 
@@ -135,3 +138,78 @@ def ksum(wave, x, even_only=False, fill=np.nan):
     _check(lib().du_ksum(C.c_int(wave), C.c_int(T), C.c_int(int(even_only)), _p(x, C.c_double), _p(ls, C.c_double),
                          _p(lc, C.c_double), _p(o, C.c_double), C.c_int(n)), f"du_ksum({wave})")
     return ls, lc, o
+
+
+# ------------------------------------------------------------------------------- dsq_wide.h / dsq_wider.h / dsq_linalg.h
+def wide_ld(P):
+    return P | 1
+
+
+def _d(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def gram(mp, two, Xt, w0, w1=None, N=None, blocks=0):
+    """WideGram<Wv, two, mp> over the product's call sequence.  Xt: [G][P][ldx], w0 / w1: [G][N] (N <= ldx) ->
+    (M, dM), each [G][P][ld] as the workspace holds them; what the kernel did not write is NaN."""
+    Xt, w0 = _d(Xt), _d(w0)
+    G, P, ldx = Xt.shape
+    N = w0.shape[1] if N is None else N
+    w1 = _d(w1) if w1 is not None else None
+    if w0.shape != (G, N) or (w1 is not None and w1.shape != (G, N)):
+        raise ValueError("w0 / w1 must be [G][N]")
+    M = np.full((G, P, wide_ld(P)), np.nan)
+    dM = np.full_like(M, np.nan)
+    _check(lib().du_gram(C.c_int(mp), C.c_int(int(two)), C.c_int(P), C.c_int(N), C.c_int(ldx), C.c_int(G),
+                         C.c_int(blocks), _p(Xt, C.c_double), _p(w0, C.c_double), _p(w1, C.c_double),
+                         _p(M, C.c_double), _p(dM, C.c_double)), f"du_gram({mp}, {two}, P={P}, N={N})")
+    return M, dM
+
+
+def wide_linalg(mp, op, P, in0, in1=None, diag_add=0.0, cells=0, blocks=0):
+    """One op of LIN_OPS per gene.  in0 / in1: [G][...] (dense P x P matrices, P vectors, xs as [P][64], Xc as [C][P],
+    cell sums [C]).  Returns [G][nout]: P x ld for chol / cells, 2 x P x ld (Li, inv) for inverse, P for solve, the 64
+    lanes' values for logdet / frob / quad_xs."""
+    in0 = _d(in0)
+    G = in0.shape[0]
+    in0 = in0.reshape(G, -1)
+    in1 = _d(in1).reshape(G, -1) if in1 is not None else None
+    ld = wide_ld(P)
+    nout = {"chol": P * ld, "cells": P * ld, "inverse": 2 * P * ld, "solve": P}.get(op, 64)
+    out = np.full((G, nout), np.nan)
+    _check(lib().du_wide_linalg(C.c_int(mp), C.c_int(LIN_OPS.index(op)), C.c_int(P), C.c_int(G), C.c_int(blocks),
+                                C.c_int(cells), C.c_double(diag_add), _p(in0, C.c_double), C.c_int(in0.shape[1]),
+                                _p(in1, C.c_double), C.c_int(in1.shape[1] if in1 is not None else 0),
+                                _p(out, C.c_double), C.c_int(nout)), f"du_wide_linalg({mp}, {op}, P={P})")
+    return out
+
+
+def irls_rhs(mp, Xt, y, sf, beta, disp, min_mu, a, blocks=0):
+    """One irls_sweep_wide (no cells) at beta.  Xt: [G][P][ldx], y / sf: [G][N], beta: [G][P] ->
+    (W.v(1) [G][P], W.M [G][P][ld])."""
+    Xt, sf, beta = _d(Xt), _d(sf), _d(beta)
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    G, P, ldx = Xt.shape
+    N = y.shape[1]
+    if y.shape != (G, N) or sf.shape != (G, N) or beta.shape != (G, P):
+        raise ValueError("y / sf must be [G][N], beta [G][P]")
+    v1 = np.full((G, P), np.nan)
+    M = np.full((G, P, wide_ld(P)), np.nan)
+    _check(lib().du_irls_rhs(C.c_int(mp), C.c_int(P), C.c_int(N), C.c_int(ldx), C.c_int(G), C.c_int(blocks),
+                             _p(Xt, C.c_double), _p(y, C.c_int), _p(sf, C.c_double), _p(beta, C.c_double),
+                             C.c_double(disp), C.c_double(min_mu), C.c_double(a), _p(v1, C.c_double),
+                             _p(M, C.c_double)), f"du_irls_rhs({mp}, P={P}, N={N})")
+    return v1, M
+
+
+def row_solve(P, ent, ridge, even_only=False):
+    """row_chol_solve<RowWave, P>: ent [G][P (P + 1) / 2 + P] (packed lower triangle, then b) -> x [G][16 lanes][P];
+    rows that left early (even_only: genes 1 and 3 of every four) keep NaN."""
+    ent = _d(ent)
+    G = ent.shape[0]
+    if ent.shape != (G, P * (P + 1) // 2 + P):
+        raise ValueError("ent must be [G][T + P]")
+    x = np.full((G, 16, P), np.nan)
+    _check(lib().du_row_solve(C.c_int(P), C.c_int(G), C.c_int(int(even_only)), _p(ent, C.c_double),
+                              C.c_double(ridge), _p(x, C.c_double)), f"du_row_solve({P})")
+    return x

@@ -8,7 +8,10 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SRC = os.path.join(HERE, "devunit.hip")
+SRC = os.path.join(HERE, "devunit.hip")  # dsq_math.h, dsq_wave.h
+SRC_LINALG = os.path.join(HERE, "devunit_linalg.hip")  # dsq_wide.h, dsq_wider.h, row_chol_solve
+SRCS = [SRC, SRC_LINALG]
+HOST_H = os.path.join(HERE, "devunit_host.h")
 OUT = os.path.join(HERE, "_devunit.so")
 INC = os.path.join(ROOT, "pydeseq2_amd", "csrc")
 MAKEFILE = os.path.join(INC, "Makefile")
@@ -38,16 +41,17 @@ def cxxflags():
 
 
 def compile_cmd(out=OUT):
-    return [HIPCC, *cxxflags(), "-shared", "-I", INC, SRC, "-o", out]
+    return [HIPCC, *cxxflags(), "-shared", "-I", INC, *SRCS, "-o", out]
 
 
 def asm_cmd(out):
-    """Device assembly of the library: shows which branches of the headers the device build took."""
-    return [HIPCC, *cxxflags(), "--cuda-device-only", "-S", "-I", INC, SRC, "-o", out]
+    """Device assembly of the library: shows which branches of the headers the device build took.  One output file
+    takes one input, so the second unit is read in front of the first (-include); their names do not collide."""
+    return [HIPCC, *cxxflags(), "--cuda-device-only", "-S", "-I", INC, "--include=" + SRC_LINALG, SRC, "-o", out]
 
 
 def build(force=False):
-    deps = [SRC, MAKEFILE] + [os.path.join(INC, f) for f in os.listdir(INC) if f.endswith(".h")]
+    deps = [*SRCS, HOST_H, MAKEFILE] + [os.path.join(INC, f) for f in os.listdir(INC) if f.endswith(".h")]
     deps.append(os.path.join(ROOT, "include", "deseq_hip.h"))
     if not force and os.path.exists(OUT) and all(
         os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps

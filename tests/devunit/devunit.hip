@@ -12,8 +12,7 @@
 // synchronises and frees on its own and returns the first hipError_t (hipErrorInvalidValue for a bad argument).
 #include <hip/hip_runtime.h>
 
-#include <vector>
-
+#include "devunit_host.h"
 #include "dsq_alpha.h"
 #include "dsq_alpha_rows.h"
 #include "dsq_irls.h"
@@ -22,41 +21,11 @@
 #include "dsq_wave.h"
 
 using namespace dsq;
+using devunit::Bufs;
 
 namespace {
 
 constexpr int kB = 256;  // threads per block
-
-// device buffers of one call; the first error sticks
-struct Bufs {
-    std::vector<void*> p;
-    hipError_t e = hipSuccess;
-    ~Bufs() {
-        for (void* q : p) (void)hipFree(q);
-    }
-    void chk(hipError_t r) {
-        if (e == hipSuccess) e = r;
-    }
-    // device copy of n host elements (output buffers too: entries a kernel leaves alone keep the host's values)
-    template <class T>
-    T* put(const T* h, size_t n) {
-        if (e != hipSuccess || h == nullptr) return nullptr;
-        void* d = nullptr;
-        chk(hipMalloc(&d, n * sizeof(T)));
-        if (e != hipSuccess) return nullptr;
-        p.push_back(d);
-        chk(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
-        return (T*)d;
-    }
-    template <class T>
-    void get(T* h, const T* d, size_t n) {
-        if (e == hipSuccess && h != nullptr && d != nullptr) chk(hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost));
-    }
-    void done() {
-        chk(hipGetLastError());
-        chk(hipDeviceSynchronize());
-    }
-};
 
 bool bad_n(int n) { return n <= 0 || n % kB != 0; }
 
