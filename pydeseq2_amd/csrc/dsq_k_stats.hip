@@ -13,62 +13,11 @@
 
 #include "dsq_dispatch.h"
 #include "dsq_launch.h"
+#include "dsq_lds_sort.h"
 #include "dsq_stats.h"
 #include "dsq_trend.h"
 
 namespace dsq {
-
-// ------------------------------------------------------------------ wave-private LDS sort
-// Bitonic sort of n doubles (padded to L = next pow2 with +inf) held in a wave-private LDS
-// segment; lanes stride over compare-exchange pairs.  Only this wave touches the segment,
-// LDS operations of one wave execute in order, so a wave-level fence is sufficient.
-struct LdsSorter {
-    __device__ __forceinline__ static void wave_sync() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    __device__ __forceinline__ int operator()(double* buf, int n) const {
-        int L = 1;
-        while (L < n) L <<= 1;
-        const int lane = threadIdx.x & 63;
-        for (int k = n + lane; k < L; k += 64) buf[k] = INFINITY;
-        wave_sync();
-        for (int k = 2; k <= L; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = lane; i < (L >> 1); i += 64) {
-                    const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));
-                    const int hi = lo | j;
-                    const bool up = ((lo & k) == 0);
-                    const double a = buf[lo], b = buf[hi];
-                    // NaNs sort last (numpy.sort semantics)
-                    const bool gt = (a > b) || (a != a && b == b);
-                    if (gt == up) { buf[lo] = b; buf[hi] = a; }
-                }
-                wave_sync();
-            }
-        }
-        return L;
-    }
-    // buf[0..n) bitonic (here: decreasing then increasing), buf[n..L) = +inf from the preceding sort:
-    // the final merge phase of the network alone leaves it ascending
-    __device__ __forceinline__ void merge(double* buf, int n) const {
-        int L = 1;
-        while (L < n) L <<= 1;
-        const int lane = threadIdx.x & 63;
-        wave_sync();
-        for (int j = L >> 1; j > 0; j >>= 1) {
-            for (int i = lane; i < (L >> 1); i += 64) {
-                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));
-                const int hi = lo | j;
-                const double a = buf[lo], b = buf[hi];
-                const bool gt = (a > b) || (a != a && b == b);
-                if (gt) { buf[lo] = b; buf[hi] = a; }
-            }
-            wave_sync();
-        }
-    }
-};
 
 // ------------------------------------------------------------------ transposes
 // sample-major [N][G] (SrcT) -> gene-major [G][ldn] (DstT) through a 64x65 LDS tile

@@ -779,7 +779,7 @@ DSQ_HD double seg_trimmed_variances(const int32_t* y, const double* sf, const Ce
     for (int e = Wv::lane(); e < kSegBatch; e += Wv::W) {
         int k, n, nt, cls, beg;
         cell_of_elem(e, k, n, nt, cls, beg);
-        double v = INFINITY;
+        double v = NAN;  // (padding: sorts behind the cell's own NaNs, as in LdsSorter; +inf would push them out of the cell)
         if (k < n) {
             const int sidx = C.cell_index[beg + k];
             v = (double)y[sidx] / sf[sidx];
@@ -829,7 +829,8 @@ DSQ_HD double seg_trimmed_variances(const int32_t* y, const double* sf, const Ce
 }
 
 // The k-th normalised count of a design cell (y / sf, as y * (1 / sf)), or its squared error against `tm`; -1 for a
-// zero count (inactive for bucket_rank_sum) - recomputed from the gene's row on every access instead of being kept in
+// zero count (inactive for bucket_rank_sum; over a size factor of 0 or NaN the count is NaN like any other, and the
+// callers' `bad` test sends the gene to the path that orders NaNs as numpy.sort does) - recomputed from the gene's row on every access instead of being kept in
 // a wave-private LDS buffer: the row is read from L1 / L2 three more times, the LDS footprint of a wavefront drops from
 // next_pow2(N) doubles (64 KB at N = 5000: two wavefronts per CU) to the bucket table (8 KB)
 struct NormedValues {
@@ -841,8 +842,8 @@ struct NormedValues {
     DSQ_HD double operator[](int k) const {
         const int s = idx != nullptr ? idx[k] : k;
         const int yi = y[s];
-        if (yi == 0) return -1.0;
         const double v = (double)yi * frcp_g(sf[s]);
+        if (yi == 0 && v == v) return -1.0;  // (0 / 0 and 0 / NaN stay NaN, as the reference's division leaves them)
         if (!squared) return v;
         const double d = v - tm;
         return d * d;
@@ -883,7 +884,7 @@ DSQ_HD void fetch_batch(const NormedValues& V, int k0, int stride, int n, double
             const double d = x - V.tm;
             x = d * d;
         }
-        v[u] = yi[u] == 0 ? -1.0 : x;
+        v[u] = (yi[u] == 0 && x == x) ? -1.0 : x;  // (a zero count over a size factor of 0 or NaN: NaN, not a zero)
     }
 }
 
@@ -1036,7 +1037,7 @@ DSQ_HD double robust_disp_gene(const int32_t* y, const double* sf, const CellPla
         m = Wv::sum(s) / (double)N;
     }
     double ar = (vmax - m) / (m * m);
-    ar = (ar > 0.04) ? ar : 0.04;  // np.maximum(alpha, 0.04) (NaN -> stays NaN in numpy; see below)
+    ar = (ar < 0.04) ? 0.04 : ar;  // np.maximum(alpha, 0.04): a NaN - of the variance or of the mean - stays NaN
     if (vmax != vmax) ar = vmax;
     return ar;
 }
@@ -1124,7 +1125,7 @@ DSQ_HD double robust_disp_gene_lean(const int32_t* y, const double* sf, const Ce
         m = Wv::sum(s) / (double)N;
     }
     double ar = (vmax - m) / (m * m);
-    ar = (ar > 0.04) ? ar : 0.04;
+    ar = (ar < 0.04) ? 0.04 : ar;  // (as robust_disp_gene)
     if (vmax != vmax) ar = vmax;
     return ar;
 }
@@ -1237,8 +1238,10 @@ DSQ_HD double trimmed_base_mean(const int32_t* y, const double* sf, int N, doubl
         int zeros = 0;
         for (int k = Wv::lane(); k < N; k += Wv::W) {
             const int yi = y[k];
-            scratch[k] = yi == 0 ? -1.0 : (double)yi / sf[k];
-            zeros += yi == 0 ? 1 : 0;
+            const double q = (double)yi / sf[k];
+            const bool zero = yi == 0 && q == q;  // (0 / 0, 0 / NaN: NaN - the bucket pass refuses, the sort orders it last)
+            scratch[k] = zero ? -1.0 : q;
+            zeros += zero ? 1 : 0;
         }
         zeros = Wv::sumi(zeros);
         Wv::sync();
@@ -1260,7 +1263,8 @@ struct ExactNormedValues {
     const double* sf;
     DSQ_HD double operator[](int k) const {
         const int yi = y[k];
-        return yi == 0 ? -1.0 : (double)yi / sf[k];
+        const double q = (double)yi / sf[k];
+        return (yi == 0 && q == q) ? -1.0 : q;
     }
 };
 template <class Wv>

@@ -1,5 +1,5 @@
 """ctypes front-end of the TEST-ONLY device build of dsq_math.h / dsq_wave.h (see devunit.hip) and of dsq_wide.h /
-dsq_wider.h / row_chol_solve (see devunit_linalg.hip).
+dsq_wider.h / row_chol_solve (see devunit_linalg.hip) and of dsq_stats.h / dsq_lds_sort.h (see devunit_stats.hip).
 
 Every function takes numpy arrays, pads them to whole 256-thread blocks where the caller has not, runs one entry point
 (allocate, copy, launch, synchronise, free) and raises on a non-zero hipError_t."""
@@ -213,3 +213,120 @@ def row_solve(P, ent, ridge, even_only=False):
     _check(lib().du_row_solve(C.c_int(P), C.c_int(G), C.c_int(int(even_only)), _p(ent, C.c_double),
                               C.c_double(ridge), _p(x, C.c_double)), f"du_row_solve({P})")
     return x
+
+
+# ------------------------------------------------------------------------------- dsq_stats.h / dsq_lds_sort.h
+def _proto():
+    """argument types of the devunit_stats.hip entry points (set once per process)"""
+    L = lib()
+    if getattr(L, "_stats_proto", False):
+        return L
+    pd, pi, p32, pu8 = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    for f in (L.du_lds_sort, L.du_lds_merge, L.du_lds_sort_merge):
+        f.argtypes = [pd, pi, C.c_int, C.c_int, pd]
+        f.restype = C.c_int
+    L.du_trimmed_select.argtypes = [pd, pi, pi, C.c_int, C.c_int, pd]
+    for f in (L.du_bucket_rank_sum, L.du_select_rank_sum):
+        f.argtypes = [pd, p32, pd, p32, pd, pi, pi, C.c_int, C.c_int, pd, pi]
+        f.restype = C.c_int
+    L.du_seg_variances.argtypes = [p32, pd, p32, p32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, pd]
+    L.du_cooks_acc.argtypes = [C.c_int, p32, pd, pd, pu8, C.c_int, C.c_int, C.c_int, pd, C.c_double, C.c_int, pd, pi]
+    for f in (L.du_trimmed_select, L.du_seg_variances, L.du_cooks_acc):
+        f.restype = C.c_int
+    L._stats_proto = True
+    return L
+
+
+def _rows(rows, dtype=np.float64):
+    """rows of different lengths -> (concatenated values, offsets [len + 1])"""
+    off = np.zeros(len(rows) + 1, np.int32)
+    off[1:] = np.cumsum([len(r) for r in rows])
+    flat = np.concatenate([np.asarray(r, dtype=dtype).ravel() for r in rows]) if rows else np.zeros(0, dtype)
+    return np.ascontiguousarray(flat, dtype=dtype), off
+
+
+def _split(flat, off):
+    return [flat[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+def lds_sort(rows, fill=0, merge=False):
+    """LdsSorter::operator() on every row (merge = True: ::merge; merge = "after sort": the product's sequence sort,
+    squared errors around the sorted row's element n // 3, merge); the rows as the sorter leaves them."""
+    v, off = _rows(rows)
+    out = np.full_like(v, -7.0)
+    name = {False: "du_lds_sort", True: "du_lds_merge", "after sort": "du_lds_sort_merge"}[merge]
+    _check(getattr(_proto(), name)(_p(v, C.c_double), _p(off, C.c_int), len(rows), fill, _p(out, C.c_double)), name)
+    return _split(out, off)
+
+
+def trimmed_select(rows, nts, fill=0):
+    """trimmed_sum_select(row, n, nt) per row"""
+    v, off = _rows(rows)
+    nt = np.ascontiguousarray(nts, dtype=np.int32)
+    out = np.full(len(rows), np.nan)
+    _check(_proto().du_trimmed_select(_p(v, C.c_double), _p(off, C.c_int), _p(nt, C.c_int), len(rows), fill,
+                                      _p(out, C.c_double)), "du_trimmed_select")
+    return out
+
+
+def rank_sum(problems, select, use_range, fill=0):
+    """bucket_rank_sum (select: select_rank_sum) per problem.  A problem is a dict with j_lo, j_hi and either v (a
+    buffer of doubles, -1 = inactive) or y, sf, idx (None: samples in order), tm, squared (a NormedValues accessor).
+    Returns (sums, accepted flags)."""
+    n_prob = len(problems)
+    acc_mode = ["y" in q for q in problems]
+    lens = [len(q["y"] if a else q["v"]) for q, a in zip(problems, acc_mode)]
+    v, off = _rows([q["v"] if not a else np.zeros(n) for q, a, n in zip(problems, acc_mode, lens)])
+    y, _ = _rows([q["y"] if a else np.zeros(n) for q, a, n in zip(problems, acc_mode, lens)], np.int32)
+    sf, _ = _rows([q["sf"] if a else np.ones(n) for q, a, n in zip(problems, acc_mode, lens)])
+    idx, _ = _rows([q["idx"] if a and q.get("idx") is not None else np.arange(n)
+                    for q, a, n in zip(problems, acc_mode, lens)], np.int32)
+    tm = np.array([float(q.get("tm", 0.0)) for q in problems])
+    ip = np.zeros((n_prob, 4), np.int32)
+    for i, (q, a) in enumerate(zip(problems, acc_mode)):
+        n_act = int((np.asarray(q["y"]) != 0).sum()) if a else int((~(np.asarray(q["v"]) < 0)).sum())
+        mode = int(bool(select)) | (int(bool(use_range)) << 1) | (int(a) << 2)
+        if a:
+            mode |= (int(bool(q.get("squared", False))) << 3) | (int(q.get("idx") is not None) << 4)
+        ip[i] = (n_act, q["j_lo"], q["j_hi"], mode)
+    out, ok = np.full(n_prob, np.nan), np.full(n_prob, -7, np.int32)
+    entry = _proto().du_select_rank_sum if select else _proto().du_bucket_rank_sum
+    _check(entry(_p(v, C.c_double), _p(y, C.c_int32), _p(sf, C.c_double), _p(idx, C.c_int32),
+                                _p(tm, C.c_double), _p(off, C.c_int), _p(ip, C.c_int), n_prob, fill,
+                                _p(out, C.c_double), _p(ok, C.c_int)), "du_select_rank_sum" if select else "du_bucket_rank_sum")
+    return out, ok
+
+
+def seg_variances(y, sf, sizes, index, L, fill=0):
+    """One seg_trimmed_variances pass per batch of 128 / L cells from vmax = -inf.  y: [G][N] counts, sizes: the
+    cells' sizes, index: their sample ids one cell after the other.  Returns [G][n_cells]: lane q of batch b holds
+    cell b * (128 / L) + q; and the lanes beyond the cells of every batch, which must still hold -inf."""
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    G, N = y.shape
+    sf = np.ascontiguousarray(sf, dtype=np.float64)
+    co = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    ci = np.ascontiguousarray(index, dtype=np.int32)
+    nc, per = len(sizes), 128 // L
+    nb = -(-nc // per)
+    out = np.full((G, nb, 64), np.nan)
+    _check(_proto().du_seg_variances(_p(y, C.c_int32), _p(sf, C.c_double), _p(co, C.c_int32), _p(ci, C.c_int32), nc, N, G,
+                                     L, fill, _p(out, C.c_double)), "du_seg_variances")
+    cells = np.concatenate([out[:, b, :min(per, nc - b * per)] for b in range(nb)], axis=1)
+    rest = np.concatenate([out[:, b, min(per, nc - b * per):] for b in range(nb)], axis=1)
+    return cells, rest
+
+
+def cooks_acc(y, mu, hat, flags, ar, cutoff, P, counted=False, fill=0):
+    """CooksAcc<DeviceWave>: add() over every sample, then finish() (counted: finish_counted with a counting lambda).
+    y / mu / hat: [G][N].  Returns (ck [G][N], ints [G][6]: any_gt_all, any_gt_use, any_gt_use_nr, few_above, the
+    winner's index, the winner's count)."""
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    G, N = y.shape
+    mu, hat = _d(mu), _d(hat)
+    fl = np.ascontiguousarray(flags, dtype=np.uint8)
+    ar = np.ascontiguousarray(np.broadcast_to(np.asarray(ar, dtype=np.float64), (G,)))
+    ck, io = np.full((G, N), -7.0), np.full((G, 6), -7, np.int32)
+    _check(_proto().du_cooks_acc(int(counted), _p(y, C.c_int32), _p(mu, C.c_double), _p(hat, C.c_double), _p(fl, C.c_uint8),
+                                 N, G, P, _p(ar, C.c_double), float(cutoff), fill, _p(ck, C.c_double), _p(io, C.c_int)),
+           "du_cooks_acc")
+    return ck, io

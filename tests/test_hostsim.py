@@ -13,6 +13,7 @@ from scipy.stats import norm
 
 from oracle import nbglm_oracle as orc
 from tests import hostsim as hs
+from tests import stats_cases as sc
 from tests.helpers import assert_close, check_hard_dispersion_genes, check_hard_lfc_genes, load_kat
 
 CASES = ["p1", "p2", "p3", "p4", "p5", "p6", "p7", "p8", "p8m", "p9", "p10", "p11", "p12"]
@@ -326,11 +327,11 @@ def test_trimmed_sum_by_selection_matches_sort():
     rng = np.random.default_rng(12)
     cases = []
     for n in (1, 2, 3, 7, 24, 100, 500, 1000):
-        cases.append(rng.integers(0, 6, n) / 1.37)                       # heavy ties
-        cases.append(rng.normal(0, 1, n) * 10 ** rng.uniform(-3, 6))      # mixed signs
-        cases.append(1000.0 + rng.uniform(0, 1e-9, n))                    # shared leading bytes
-        cases.append(np.full(n, 3.25))                                    # all equal
-        cases.append(rng.negative_binomial(2, 0.01, n) / rng.uniform(0.5, 2, n))
+        cases.append(sc.heavy_ties(rng, n))
+        cases.append(sc.mixed_signs(rng, n))
+        cases.append(sc.shared_leading_bytes(rng, n))
+        cases.append(sc.all_equal(n))
+        cases.append(sc.nb_over_size_factors(rng, n))
     for v in cases:
         n = len(v)
         for nt in sorted({0, n // 8, n // 4, n // 3, (n - 1) // 2}):
@@ -399,15 +400,14 @@ def test_rank_sums_by_selection_over_an_accessor():
     for n in (1, 2, 5, 64, 129, 1000, 20000):
         for kind in range(4):
             if kind == 0:
-                v = rng.integers(1, 7, n) / 1.37
+                v = sc.heavy_ties(rng, n, 1, 7)
             elif kind == 1:
-                v = rng.negative_binomial(2, 0.01, n) / rng.uniform(0.5, 2, n) + 1e-3
+                v = sc.nb_over_size_factors(rng, n, 1e-3)
             elif kind == 2:
-                v = 1000.0 + rng.uniform(0, 1e-9, n)
+                v = sc.shared_leading_bytes(rng, n)
             else:
-                v = np.full(n, 3.25)
-            v = v.astype(float)
-            v[rng.random(n) < 0.3] = -1.0  # inactive
+                v = sc.all_equal(n)
+            v = sc.with_inactive(rng, v)
             act = np.sort(v[v >= 0])
             m = len(act)
             for (a, b) in {(0, m - 1), (m // 8, m - m // 8 - 1), (m // 3, m // 3), (m // 2, m // 2 - 1), (0, 0)}:
@@ -657,6 +657,24 @@ def test_robust_dispersion_large_cells_bucket_path(kind):
     assert_close(rd, ref, 1e-10, 1e-13, "robust dispersions")
     # the replacement value of the outlier refit (dds.py:1332-1352) takes the same bucket path
     assert_close(hs.trimmed_base_mean(counts, sf, 0.2), orc.trimmed_mean(normed, 0.2, axis=0), 1e-12, 1e-300, "trimmed mean")
+
+
+@pytest.mark.parametrize("bad", [0.0, np.nan])
+def test_robust_dispersion_keeps_the_nan_of_a_non_finite_mean(bad):
+    """A size factor of 0 or NaN under a positive count: the mean of the normalised counts is inf / NaN, and
+    np.maximum(alpha, 0.04) (utils.py:959) keeps the NaN of (v - m) / m^2 - it is not floored to 0.04.  Sorted cells and
+    the bucket path."""
+    rng = np.random.default_rng(4)
+    for N in (60, 400):
+        X = np.column_stack([np.ones(N), (np.arange(N) % 2).astype(float)])
+        sf = np.exp(rng.normal(0, 0.3, N))
+        counts = rng.negative_binomial(2.0, 2.0 / (2.0 + 50 * sf[:, None] * np.ones((1, 6)))).astype(np.int64) + 1
+        sf[7] = bad
+        with np.errstate(all="ignore"):
+            ref = orc.robust_mom_disp(counts / sf[:, None], X)
+        assert np.isnan(ref).all()
+        _, rd, _ = hs.cooks(counts, sf, X, np.ones((N, 6)), np.full((N, 6), 0.01), 10.0)
+        assert_close(rd, ref, 1e-10, 0, f"robust dispersions N={N}")
 
 
 @pytest.mark.parametrize("shape", ["3factor_500", "3factor_90", "ragged"])
