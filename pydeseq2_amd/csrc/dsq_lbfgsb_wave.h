@@ -70,8 +70,8 @@ __device__ __forceinline__ double colsum(double v) {
 namespace wv32 {
 // lane = 2 i + jg: two lanes hold row i
 __device__ __forceinline__ double rowsum(double v) { return v + detail::dpp_d<detail::kXor1>(v); }
-// over the 32 lanes that share lane & 1: + 8, + 4 inside a 16-lane row (in that order: the second relies on the period
-// the first leaves), xor 2, then xor 16, xor 32
+// over the 32 lanes that share lane & 1: + 8, + 4 inside a 16-lane row (the four lanes = l mod 4; the two rotations
+// commute - the order only fixes the rounding), xor 2, then xor 16, xor 32
 __device__ __forceinline__ double colsum(double v) {
     double a, c;
     v += detail::dpp_d<detail::kRor8>(v);
@@ -82,6 +82,62 @@ __device__ __forceinline__ double colsum(double v) {
     return v;
 }
 }  // namespace wv32
+
+// the 8-, 16- or 32-lane sums of the R x R layout
+template <int R>
+__device__ __forceinline__ double wv_rowsum(double v) {
+    if constexpr (R == 8) return wv8::rowsum(v);
+    else if constexpr (R == 16) return wv16::rowsum(v);
+    else return wv32::rowsum(v);
+}
+template <int R>
+__device__ __forceinline__ double wv_colsum(double v) {
+    if constexpr (R == 8) return wv8::colsum(v);
+    else if constexpr (R == 16) return wv16::colsum(v);
+    else return wv32::colsum(v);
+}
+
+// One iteration's direction: H_k from the `col` pairs in the ring slots head, head + 1, ... (mod 10) of W.S / W.Y / W.RHO
+// on I / theta, then W.d = -H_k W.g and W.z = W.x - H_k W.g (rows 0 .. R-1; all lanes call it, barrier included).
+// lbfgsb_wave's only use of the matrix - tests/devunit calls it on given pairs.
+template <int R>
+__device__ __forceinline__ void lbfgsb_wave_direction(LbfgsbWaveWorkT<R>& W, int col, int head, double theta) {
+    constexpr int M = 10;
+    constexpr int E = R * R / 64;  // entries per lane: 1, 4, 16
+    const int lane = threadIdx.x & 63;
+    const int i = R == 8 ? lane >> 3 : (R == 16 ? lane >> 2 : lane >> 1);                   // row of this lane's entries
+    const int j0 = R == 8 ? (lane & 7) : (R == 16 ? 4 * (lane & 3) : 16 * (lane & 1));      // their first column
+    // ------------------------------------------------------------ H_k: the pairs replayed on I / theta
+    double h[E];
+    {
+        const double ith = fdiv(1.0, theta);
+#pragma unroll
+        for (int c = 0; c < E; ++c) h[c] = (i == j0 + c) ? ith : 0.0;
+    }
+    for (int q = 0; q < col; ++q) {
+        const int p = (head + q) % M;
+        const double si = W.S[p][i], yi = W.Y[p][i], rho = W.RHO[p];
+        double sj[E], yj[E], hy_j[E], t = 0.0;
+#pragma unroll
+        for (int c = 0; c < E; ++c) { sj[c] = W.S[p][j0 + c]; yj[c] = W.Y[p][j0 + c]; t += h[c] * yj[c]; }
+        const double hy_i = wv_rowsum<R>(t);  // (H y)_i
+#pragma unroll
+        for (int c = 0; c < E; ++c) hy_j[c] = wv_colsum<R>(h[c] * yi);  // (H y)_j: H is symmetric
+        const double yhy = wv_colsum<R>(yi * hy_i);
+        const double cc = rho * yhy + 1.0;
+#pragma unroll
+        for (int c = 0; c < E; ++c) h[c] += rho * (cc * (si * sj[c]) - (si * hy_j[c] + hy_i * sj[c]));
+    }
+    // ------------------------------------------------------------ z = x - H g (Cauchy point + subspace minimisation)
+    {
+        double t = 0.0;
+#pragma unroll
+        for (int c = 0; c < E; ++c) t += h[c] * W.g[j0 + c];
+        const double hg_i = wv_rowsum<R>(t);
+        if (j0 == 0) { W.d[i] = -hg_i; W.z[i] = W.x[i] - hg_i; }
+    }
+    DeviceWave::sync();
+}
 #endif
 
 // x0 in W.x[0 .. P-1]; result in W.x.  FG: void(const double* x, double& f, double* g) (all lanes call it; g[0 .. P-1])
@@ -93,10 +149,7 @@ DSQ_HD LbfgsbResult lbfgsb_wave(FG&& fg, LbfgsbWaveWorkT<R>& W, double factr = 1
     LbfgsbResult R_;
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int M = 10;
-    constexpr int E = R * R / 64;  // entries per lane: 1, 4, 16
     const int lane = threadIdx.x & 63;
-    const int i = R == 8 ? lane >> 3 : (R == 16 ? lane >> 2 : lane >> 1);                   // row of this lane's entries
-    const int j0 = R == 8 ? (lane & 7) : (R == 16 ? 4 * (lane & 3) : 16 * (lane & 1));      // their first column
     const double epsmch = kEps, tol = factr * epsmch;
     int col = 0, head = 0, iter = 0, nfev = 0;
     double theta = 1.0, f = 0.0, fold = 0.0, gd = 0.0, gdold = 0.0, stp = 0.0;
@@ -117,16 +170,6 @@ DSQ_HD LbfgsbResult lbfgsb_wave(FG&& fg, LbfgsbWaveWorkT<R>& W, double factr = 1
         for (int k = 0; k < P; ++k) s += a[k] * b[k];
         return s;
     };
-    auto rowsum = [&](double v) {
-        if constexpr (R == 8) return wv8::rowsum(v);
-        else if constexpr (R == 16) return wv16::rowsum(v);
-        else return wv32::rowsum(v);
-    };
-    auto colsum = [&](double v) {
-        if constexpr (R == 8) return wv8::colsum(v);
-        else if constexpr (R == 16) return wv16::colsum(v);
-        else return wv32::colsum(v);
-    };
     fg(W.x, f, W.g);
     DeviceWave::sync();
     nfev = 1;
@@ -134,36 +177,8 @@ DSQ_HD LbfgsbResult lbfgsb_wave(FG&& fg, LbfgsbWaveWorkT<R>& W, double factr = 1
     if (sbgnrm <= pgtol) { R_ = {f, true, nfev, 0, 0}; return R_; }
 
     for (;;) {
-        // ------------------------------------------------------------ H_k: the pairs replayed on I / theta
-        double h[E];
-        {
-            const double ith = fdiv(1.0, theta);
-#pragma unroll
-            for (int c = 0; c < E; ++c) h[c] = (i == j0 + c) ? ith : 0.0;
-        }
-        for (int q = 0; q < col; ++q) {
-            const int p = (head + q) % M;
-            const double si = W.S[p][i], yi = W.Y[p][i], rho = W.RHO[p];
-            double sj[E], yj[E], hy_j[E], t = 0.0;
-#pragma unroll
-            for (int c = 0; c < E; ++c) { sj[c] = W.S[p][j0 + c]; yj[c] = W.Y[p][j0 + c]; t += h[c] * yj[c]; }
-            const double hy_i = rowsum(t);  // (H y)_i
-#pragma unroll
-            for (int c = 0; c < E; ++c) hy_j[c] = colsum(h[c] * yi);  // (H y)_j: H is symmetric
-            const double yhy = colsum(yi * hy_i);
-            const double cc = rho * yhy + 1.0;
-#pragma unroll
-            for (int c = 0; c < E; ++c) h[c] += rho * (cc * (si * sj[c]) - (si * hy_j[c] + hy_i * sj[c]));
-        }
-        // ------------------------------------------------------------ z = x - H g (Cauchy point + subspace minimisation)
-        {
-            double t = 0.0;
-#pragma unroll
-            for (int c = 0; c < E; ++c) t += h[c] * W.g[j0 + c];
-            const double hg_i = rowsum(t);
-            if (j0 == 0) { W.d[i] = -hg_i; W.z[i] = W.x[i] - hg_i; }
-        }
-        DeviceWave::sync();
+        // ------------------------------------------------------------ H_k replayed from the pairs; d = -H_k g, z = x + d
+        lbfgsb_wave_direction<R>(W, col, head, theta);
         // ------------------------------------------------------------ line search (dsq_lbfgsb_dense.h, nbd = 0)
         const double dtd = dot(W.d, W.d);
         const double stpmx = 1e10;

@@ -1,5 +1,6 @@
 """ctypes front-end of the TEST-ONLY device build of dsq_math.h / dsq_wave.h (see devunit.hip) and of dsq_wide.h /
-dsq_wider.h / row_chol_solve (see devunit_linalg.hip) and of dsq_stats.h / dsq_lds_sort.h (see devunit_stats.hip).
+dsq_wider.h / row_chol_solve (see devunit_linalg.hip), of dsq_stats.h / dsq_lds_sort.h (see devunit_stats.hip) and of
+dsq_lbfgsb_wave.h / dsq_lbfgsb.h / dsq_lbfgsb_par.h (see devunit_optim.hip).
 
 Every function takes numpy arrays, pads them to whole 256-thread blocks where the caller has not, runs one entry point
 (allocate, copy, launch, synchronise, free) and raises on a non-zero hipError_t."""
@@ -330,3 +331,93 @@ def cooks_acc(y, mu, hat, flags, ar, cutoff, P, counted=False, fill=0):
                                  N, G, P, _p(ar, C.c_double), float(cutoff), fill, _p(ck, C.c_double), _p(io, C.c_int)),
            "du_cooks_acc")
     return ck, io
+
+
+# ------------------------------------------------------------------------------- dsq_lbfgsb_wave.h / dsq_lbfgsb.h / _par.h
+TRACE_CAP = 256
+NAN_WORD, ZERO_WORD, FF_WORD = 0x7FF8000000000000, 0, 0xFFFFFFFFFFFFFFFF
+LBP_OPS = ["dpofa", "dtrsl01", "dtrsl11", "batch11"]
+
+
+def groupsum(R, which, v):
+    """wv8 / wv16 / wv32 (R) rowsum or colsum (which) of one value per lane: v holds whole 256-thread blocks."""
+    v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+    out = np.full_like(v, np.nan)
+    _check(lib().du_groupsum(C.c_int(R), C.c_int(["rowsum", "colsum"].index(which)), _p(v, C.c_double),
+                             _p(out, C.c_double), C.c_int(v.size)), f"du_groupsum({R}, {which})")
+    return out
+
+
+def direction(R, col, head, theta, S, Y, RHO, g, x):
+    """lbfgsb_wave_direction<R> per problem.  S, Y: [n][10][R], RHO: [n][10], g, x: [n][R] -> (d, z), each [n][R]."""
+    S, Y, RHO, g, x = _d(S), _d(Y), _d(RHO), _d(g), _d(x)
+    n = S.shape[0]
+    if S.shape != (n, 10, R) or Y.shape != S.shape or RHO.shape != (n, 10) or g.shape != (n, R) or x.shape != (n, R):
+        raise ValueError("S / Y must be [n][10][R], RHO [n][10], g / x [n][R]")
+    col = np.ascontiguousarray(col, dtype=np.int32)
+    head = np.ascontiguousarray(head, dtype=np.int32)
+    theta = _d(theta)
+    if col.shape != (n,) or head.shape != (n,) or theta.shape != (n,):
+        raise ValueError("col / head / theta must be [n]")
+    d, z = np.full((n, R), np.nan), np.full((n, R), np.nan)
+    _check(lib().du_direction(C.c_int(R), C.c_int(n), _p(col, C.c_int), _p(head, C.c_int), _p(theta, C.c_double),
+                              _p(S, C.c_double), _p(Y, C.c_double), _p(RHO, C.c_double), _p(g, C.c_double),
+                              _p(x, C.c_double), _p(d, C.c_double), _p(z, C.c_double)), f"du_direction({R})")
+    return d, z
+
+
+def optimise(form, problems, P=0, R=0, block=64, pattern=NAN_WORD):
+    """One optimiser run per problem (dicts with Q [n][n], c, w, x0 and optionally bounds, scipy's convention; one n).
+    form "wave": lbfgsb_wave<P, R>, `block` threads per block (64: a problem per block, 256: four); "one" / "lanes":
+    lbfgsb_nd<R, ., 10, OneLane / DeviceWave>.  The workspace holds `pattern` in every 64-bit word before x0 goes in.
+    Returns a list of dicts: x, f, g (the evaluations, in order, at most TRACE_CAP), nev (evaluations made), xfin, ffin,
+    success, nfev, nit, status."""
+    n = len(problems[0]["c"])
+    k = len(problems)
+    Q = _d([q["Q"] for q in problems])
+    c, w, x0 = (_d([q[key] for q in problems]) for key in ("c", "w", "x0"))
+    if Q.shape != (k, n, n) or c.shape != (k, n) or w.shape != (k, n) or x0.shape != (k, n):
+        raise ValueError("the problems of one call share n")
+    l, u, nbd = np.zeros((k, n)), np.zeros((k, n)), np.zeros((k, n), np.int32)
+    for i, q in enumerate(problems):
+        for j, (lo, hi) in enumerate(q.get("bounds") or [(None, None)] * n):
+            has_l, has_u = lo is not None and np.isfinite(lo), hi is not None and np.isfinite(hi)
+            l[i, j], u[i, j] = (lo if has_l else 0.0), (hi if has_u else 0.0)
+            nbd[i, j] = {(False, False): 0, (True, False): 1, (True, True): 2, (False, True): 3}[(has_l, has_u)]
+    if form == "wave" and nbd.any():
+        raise ValueError("lbfgsb_wave takes no bounds")
+    tx, tg = np.full((k, TRACE_CAP, n), np.nan), np.full((k, TRACE_CAP, n), np.nan)
+    tf, xo, fo = np.full((k, TRACE_CAP), np.nan), np.full((k, n), np.nan), np.full(k, np.nan)
+    res = np.full((k, 5), -7, np.int32)
+    f = lib().du_optimise
+    f.argtypes = [C.c_int] * 6 + [C.c_uint64] + [C.POINTER(C.c_double)] * 6 + [C.POINTER(C.c_int)] + \
+        [C.POINTER(C.c_double)] * 5 + [C.POINTER(C.c_int)]
+    f.restype = C.c_int
+    _check(f(["wave", "one", "lanes"].index(form), P, R, block, n, k, pattern, _p(Q, C.c_double), _p(c, C.c_double),
+             _p(w, C.c_double), _p(x0, C.c_double), _p(l, C.c_double), _p(u, C.c_double), _p(nbd, C.c_int),
+             _p(tx, C.c_double), _p(tf, C.c_double), _p(tg, C.c_double), _p(xo, C.c_double), _p(fo, C.c_double),
+             _p(res, C.c_int)), f"du_optimise({form}, P={P}, R={R}, n={n})")
+    out = []
+    for i in range(k):
+        nev = int(res[i, 4])
+        m = min(max(nev, 0), TRACE_CAP)
+        out.append(dict(x=tx[i, :m], f=tf[i, :m], g=tg[i, :m], nev=nev, xfin=xo[i], ffin=fo[i], success=bool(res[i, 0]),
+                        nfev=int(res[i, 1]), nit=int(res[i, 2]), status=int(res[i, 3])))
+    return out
+
+
+def lbp(wave64, op, lda, ns, a, b=None, sacc=None):
+    """lbp::dpofa / dtrsl_upper (jobs 01, 11) / the batch of dtrsl_upper_t_own on columns n + 1 .. 2 n (LBP_OPS) with
+    DeviceWave (wave64) or OneLane, both on the device.  a: [k][lda][lda] as the routine indexes it (a[p].ravel()[(i - 1)
+    + (j - 1) lda]), b / sacc: [k][lda] (default NaN).  Returns (a, b, sacc, ret [k][64]: every lane's return value)."""
+    a = _d(a).copy()
+    k = a.shape[0]
+    if a.shape != (k, lda, lda):
+        raise ValueError("a must be [k][lda][lda]")
+    b = _d(b).copy() if b is not None else np.full((k, lda), np.nan)
+    sacc = _d(sacc).copy() if sacc is not None else np.full((k, lda), np.nan)
+    ns = np.ascontiguousarray(ns, dtype=np.int32)
+    ret = np.full((k, 64), -7, np.int32)
+    _check(lib().du_lbp(C.c_int(int(wave64)), C.c_int(LBP_OPS.index(op)), C.c_int(lda), C.c_int(k), _p(ns, C.c_int),
+                        _p(a, C.c_double), _p(b, C.c_double), _p(sacc, C.c_double), _p(ret, C.c_int)), f"du_lbp({op})")
+    return a, b, sacc, ret

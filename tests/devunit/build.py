@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 SRC = os.path.join(HERE, "devunit.hip")  # dsq_math.h, dsq_wave.h
 SRC_LINALG = os.path.join(HERE, "devunit_linalg.hip")  # dsq_wide.h, dsq_wider.h, row_chol_solve
 SRC_STATS = os.path.join(HERE, "devunit_stats.hip")  # dsq_stats.h, dsq_lds_sort.h
-SRCS = [SRC, SRC_LINALG, SRC_STATS]
+SRC_OPTIM = os.path.join(HERE, "devunit_optim.hip")  # dsq_lbfgsb_wave.h, dsq_lbfgsb.h, dsq_lbfgsb_par.h
+SRCS = [SRC, SRC_LINALG, SRC_STATS, SRC_OPTIM]
 HOST_H = os.path.join(HERE, "devunit_host.h")
 OUT = os.path.join(HERE, "_devunit.so")
 INC = os.path.join(ROOT, "pydeseq2_amd", "csrc")
@@ -49,7 +50,7 @@ def asm_cmd(out):
     """Device assembly of the library: shows which branches of the headers the device build took.  One output file
     takes one input, so the other units are read in front of the first (-include); their names do not collide."""
     return [HIPCC, *cxxflags(), "--cuda-device-only", "-S", "-I", INC, "--include=" + SRC_LINALG, "--include=" + SRC_STATS,
-            SRC, "-o", out]
+            "--include=" + SRC_OPTIM, SRC, "-o", out]
 
 
 def build(force=False):

@@ -1,5 +1,5 @@
 // devunit_host.h — the host side every entry point of the TEST-ONLY device library shares (devunit.hip,
-// devunit_linalg.hip, devunit_stats.hip): the device buffers of one call, whose first error sticks.
+// devunit_linalg.hip, devunit_stats.hip, devunit_optim.hip): the device buffers of one call, whose first error sticks.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -301,6 +301,11 @@ def lbfgsb_dense(fg, x0, bounds):
     return lbfgsb_nd(fg, x0, bounds, entry="hs_lbfgsb_dense")
 
 
+def lbfgsb_nd48(fg, x0, bounds):
+    """lbfgsb_nd on LbfgsbWork<48> (n <= 48): the compact form at the widths the device runs it with 64 lanes"""
+    return lbfgsb_nd(fg, x0, bounds, entry="hs_lbfgsb_nd48")
+
+
 def lbfgsb_nd(fg, x0, bounds, entry="hs_lbfgsb_nd"):
     """bounds: list of (lo, hi) with None/inf for unbounded (scipy convention)."""
     n = len(x0)

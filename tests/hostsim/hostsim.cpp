@@ -552,6 +552,18 @@ int hs_lbfgsb_nd(fgn_cb cb, int n, double* x, const double* l, const double* u, 
     return 0;
 }
 
+// the same routine on the workspace of the widest compact-form shrinkage kernel (33 ... 48 coefficients on the device)
+int hs_lbfgsb_nd48(fgn_cb cb, int n, double* x, const double* l, const double* u, const int* nbd,
+                   double* f, int* success, int* nfev, int* nit, int* status) {
+    if (n < 1 || n > 48) return -1;
+    static LbfgsbWork<48> W;
+    std::memset(&W, g_hs_fill, sizeof(W));
+    auto fg = [&](const double* xx, double& ff, double* gg) { cb(xx, &ff, gg); };
+    LbfgsbResult r = lbfgsb_nd<48>(fg, n, x, l, u, nbd, W);
+    *f = r.f; *success = r.success; *nfev = r.nfev; *nit = r.nit; *status = r.status;
+    return 0;
+}
+
 int hs_trend_fit(const double* disp, const double* means, int n, double min_disp, double max_disp,
                  double* coeffs, int* ok, int* n_outer) {
     std::vector<uint8_t> keep(n + 1);

@@ -1,8 +1,8 @@
 """CPU-side checks of tests/devunit (no GPU needed: hipcc cross-compiles for gfx950).
 
 * the library builds, with exactly the CXXFLAGS that csrc/Makefile gives the product (asked of make itself);
-* its device assembly contains the device-only instructions (v_rcp_f64 / v_rsq_f64, the permlane swaps, DPP row_ror,
-  the fp64 MFMA),
+* its device assembly contains the device-only instructions (v_rcp_f64 / v_rsq_f64, the permlane swaps, DPP row_ror and
+  row_half_mirror, the fp64 MFMA),
   so the tests in test_devunit_*.py run the device branches of the headers, not the host ones;
 * the four table headers, parsed from the source, are the correctly rounded values entry by entry (mpmath, 120 bits),
   independently of the tools/gen_* scripts that wrote them."""
@@ -52,7 +52,7 @@ def test_device_assembly_takes_the_device_branches(tmp_path):
     subprocess.run(dub.asm_cmd(str(s)), check=True, capture_output=True)
     asm = s.read_text()
     for ins in ("v_rcp_f64", "v_rsq_f64", "v_permlane32_swap", "v_permlane16_swap", "row_ror:8", "row_ror:4",
-                "row_newbcast", "ds_add_f64", "ds_read_b128", "v_mfma_f64_16x16x4"):
+                "row_half_mirror", "row_newbcast", "ds_add_f64", "ds_read_b128", "v_mfma_f64_16x16x4"):
         assert ins in asm, ins
 
 

@@ -190,6 +190,25 @@ def test_lbfgsb_nd_matches_scipy():
     assert bad <= 1
 
 
+def test_lbfgsb_nd_matches_scipy_above_16_variables():
+    """The compact form on LbfgsbWork<48> - the workspace of the 33 ... 48-coefficient shrinkage kernel, whose 64-lane
+    build tests/test_devunit_optim.py holds to this one-lane build bit for bit - against scipy on the unbounded, boxed
+    and half-bounded problems of tests/optim_cases.py with more than 16 variables: same flag, same number of
+    iterations, the same point."""
+    from tests import optim_cases as oc
+
+    cases = [e for e in oc.LANES_PROBLEMS if e[2] > 16]
+    assert {e[2] for e in cases} == {33, 40, 48} and {e[4] for e in cases} == {"none", "box", "half"}
+    for entry in cases:
+        q = oc.lanes_problem(entry)
+        fg = oc.objective(q)
+        bounds = q["bounds"] or [(None, None)] * q["n"]
+        res = minimize(lambda x: fg(x)[0], q["x0"], jac=lambda x: fg(x)[1], method="L-BFGS-B", bounds=bounds)
+        x, f, ok, nfev, nit, st = hs.lbfgsb_nd48(fg, q["x0"], bounds)
+        assert ok == res.success and nit == res.nit, (entry, ok, nit, res.success, res.nit)
+        assert np.max(np.abs(x - res.x)) <= 1e-7 * max(1, np.max(np.abs(res.x))), entry
+
+
 def test_bfgs_matches_scipy():
     """The restatement of scipy's BFGS (line_search_wolfe1 = MINPACK-2 dcsrch, line_search_wolfe2 / zoom as the
     fall-back, dense inverse-Hessian update; dsq_bfgs.h) against scipy itself on random smooth and kinked problems,
