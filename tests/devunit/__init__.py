@@ -1,6 +1,7 @@
 """ctypes front-end of the TEST-ONLY device build of dsq_math.h / dsq_wave.h (see devunit.hip) and of dsq_wide.h /
 dsq_wider.h / row_chol_solve (see devunit_linalg.hip), of dsq_stats.h / dsq_lds_sort.h (see devunit_stats.hip) and of
-dsq_lbfgsb_wave.h / dsq_lbfgsb.h / dsq_lbfgsb_par.h (see devunit_optim.hip).
+dsq_lbfgsb_wave.h / dsq_lbfgsb.h / dsq_lbfgsb_par.h (see devunit_optim.hip), and of dsq_alpha.h's objective and the row
+kernels of the dispersion fit (see devunit_alpha.hip).
 
 Every function takes numpy arrays, pads them to whole 256-thread blocks where the caller has not, runs one entry point
 (allocate, copy, launch, synchronise, free) and raises on a non-zero hipError_t."""
@@ -421,3 +422,167 @@ def lbp(wave64, op, lda, ns, a, b=None, sacc=None):
     _check(lib().du_lbp(C.c_int(int(wave64)), C.c_int(LBP_OPS.index(op)), C.c_int(lda), C.c_int(k), _p(ns, C.c_int),
                         _p(a, C.c_double), _p(b, C.c_double), _p(sacc, C.c_double), _p(ret, C.c_int)), f"du_lbp({op})")
     return a, b, sacc, ret
+
+
+# ------------------------------------------------------------------------------- dsq_alpha.h, dsq_k_alpha_rows*.hip
+# (P, GRAD, PAD, NB, CELL) as devunit_alpha.hip instantiates alpha_eval (DU_EVAL_LIST)
+EVAL_INST = [(P, g, d, nb, c)
+             for P, g, d, c in ([(P, 1, 1, 0) for P in (1, 2, 3, 4, 8, 9, 12)] + [(2, 1, 0, 0), (9, 1, 0, 0), (2, 0, 0, 0),
+                                                                                 (8, 0, 0, 0), (3, 1, 1, 1), (8, 1, 1, 1)])
+             for nb in (1, 2, 4)]
+CONST_COMPUTE, CONST_STORE, CONST_LOAD = 0, 1, 2
+ROUTES = ["rows", "coef", "cell_mu"]
+SENT_D, SENT_I, SENT_U8 = -7.0, -7, 0xEE  # what the outputs hold where no kernel wrote
+STATE_D, STATE_I = ("x", "f", "g", "xold", "fold"), ("nfev", "it", "col", "done", "status")
+
+
+def _xx(Xc):
+    """x_i x_j of the cells' rows, packed lower triangle (dsq_linalg.h tri(i, j) = i (i + 1) / 2 + j)"""
+    P = Xc.shape[1]
+    ii = [i for i in range(P) for j in range(i + 1)]
+    jj = [j for i in range(P) for j in range(i + 1)]
+    return np.ascontiguousarray(Xc[:, ii] * Xc[:, jj])
+
+
+def cus():
+    return int(lib().du_cus())
+
+
+def rowsc_tail(N, P, C_):
+    """alpha_rowsc_tail: the many-cell row kernel's tail-table size for (N, P, C); 0: not eligible"""
+    return int(lib().du_rowsc_tail(int(N), int(P), int(C_)))
+
+
+def row_tail():
+    return int(lib().du_row_tail())
+
+
+def alpha_eval(inst, y, mu, X, la, la_hat, prior_var=1.0, cr_reg=True, prior_reg=False, cell_of=None, Xc=None):
+    """alpha_eval<DeviceWave, *inst> for G genes of one design.  y / mu: [G][N], X: [N][P], la / la_hat: [G] ->
+    (f [G][64], g [G][64], cst [G]): every lane's results and alpha_const of the rows.  The caller picks NB as k_alpha
+    does: a gene whose largest count is >= 64 NB needs a larger memo (NB = 4 takes any count)."""
+    P, grad, pad, nb, cell = inst
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    mu = _d(mu)
+    G, N = y.shape
+    Xt = np.ascontiguousarray(np.asarray(X, dtype=np.float64).T)
+    la, la_hat = _d(np.broadcast_to(la, (G,))), _d(np.broadcast_to(la_hat, (G,)))
+    if mu.shape != (G, N) or Xt.shape != (P, N):
+        raise ValueError("y / mu must be [G][N], X [N][P]")
+    if nb < 4 and y.max() >= 64 * nb:
+        raise ValueError("the memo does not cover the gene's largest count")
+    co = xc = xx = None
+    nc = 0
+    if cell:
+        co = np.ascontiguousarray(cell_of, dtype=np.int32)
+        xc = _d(Xc)
+        xx = _xx(xc)
+        nc = xc.shape[0]
+        if co.shape != (N,) or xc.shape[1] != P or co.min() < 0 or co.max() >= nc:
+            raise ValueError("cell_of must be [N] with values below the number of rows of Xc [C][P]")
+    f, g, cst = np.full((G, 64), np.nan), np.full((G, 64), np.nan), np.full(G, np.nan)
+    fn = lib().du_alpha_eval
+    fn.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int,
+                                   C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int,
+                                   C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int,
+                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    fn.restype = C.c_int
+    _check(fn(P, grad, pad, nb, cell, _p(y, C.c_int32), _p(mu, C.c_double), N, _p(Xt, C.c_double), N, N, G,
+              _p(la, C.c_double), _p(la_hat, C.c_double), float(prior_var), int(cr_reg), int(prior_reg),
+              _p(co, C.c_int32), _p(xc, C.c_double), _p(xx, C.c_double), nc, _p(f, C.c_double), _p(g, C.c_double),
+              _p(cst, C.c_double)), f"du_alpha_eval{inst}")
+    return f, g, cst
+
+
+def alpha_const(y, mu):
+    """(alpha_const, alpha_const_max, the largest count) of every gene as all 64 lanes return them, each [G][64]"""
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    mu = _d(mu)
+    G, N = y.shape
+    c, cm, mx = np.full((G, 64), np.nan), np.full((G, 64), np.nan), np.full((G, 64), SENT_I, np.int32)
+    fn = lib().du_alpha_const
+    fn.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                   C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    fn.restype = C.c_int
+    _check(fn(_p(y, C.c_int32), _p(mu, C.c_double), N, N, G, _p(c, C.c_double), _p(cm, C.c_double), _p(mx, C.c_int)),
+           "du_alpha_const")
+    return c, cm, mx
+
+
+def _rows_launch(entry, route, y, sf, cell_of, Xc, alpha_hat, min_disp, max_disp, min_mu, coef, cell_mu, genes,
+                 prior_var, prior_reg, const_mode, eval_cap, nll_const):
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    G, N = y.shape
+    sf, xc, ah = _d(sf), _d(Xc), _d(alpha_hat)
+    nc, P = xc.shape
+    xx = _xx(xc)
+    co = np.ascontiguousarray(cell_of, dtype=np.int32)
+    cf = _d(coef) if coef is not None else None
+    cm = _d(cell_mu) if cell_mu is not None else None
+    lst = np.ascontiguousarray(genes, dtype=np.int32) if genes is not None else None
+    n_list = lst.size if lst is not None else G
+    if sf.shape != (N,) or co.shape != (N,) or ah.shape != (G,) or (cf is not None and cf.shape != (G, P)) or \
+            (cm is not None and cm.shape != (G, nc)):
+        raise ValueError("sf / cell_of [N], alpha_hat [G], coef [G][P], cell_mu [G][C]")
+    if lst is not None and np.unique(lst).size != lst.size:
+        raise ValueError("a gene may be listed once")
+    nl = np.full(G, np.nan) if nll_const is None else _d(nll_const).copy()
+    o = dict(alpha=np.full(G, SENT_D), conv=np.full(G, SENT_U8, np.uint8), nfev=np.full(G, SENT_I, np.int32),
+             grid_list=np.full(G, SENT_I, np.int32), park_list=np.full(G, SENT_I, np.int32))
+    gc, pc, wgc = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    sd, si = np.full((G, 5), np.nan), np.full((G, 5), SENT_I, np.int32)
+    pd, pi, pu = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    common_in = [pi, C.c_int, C.c_int, C.c_int, pi, C.c_int, pd]
+    tail = [C.c_double, pd, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, pd, pd, pu, pi, pi, pi, pi, pi,
+            pd, pi]
+    common = (_p(nl, C.c_double), _p(o["alpha"], C.c_double), _p(o["conv"], C.c_uint8), _p(o["nfev"], C.c_int32),
+              _p(o["grid_list"], C.c_int32), C.byref(gc), _p(o["park_list"], C.c_int32), C.byref(pc), _p(sd, C.c_double),
+              _p(si, C.c_int32))
+    scal = (float(min_mu), _p(ah, C.c_double), float(min_disp), float(max_disp), float(prior_var), int(prior_reg),
+            int(const_mode), int(eval_cap))
+    if entry == "du_rows_trace":
+        fn = lib().du_rows_trace
+        fn.argtypes = [C.c_int] + common_in + [pd, pd, pi, pd, pd, C.c_int, C.c_int] + tail
+        fn.restype = C.c_int
+        rc = fn(ROUTES.index(route), _p(y, C.c_int32), N, N, G, _p(lst, C.c_int32), n_list, _p(cf, C.c_double),
+                _p(cm, C.c_double), _p(sf, C.c_double), _p(co, C.c_int32), _p(xc, C.c_double), _p(xx, C.c_double), nc, P,
+                *scal, *common)
+    else:
+        o.update(wg_alpha=np.full(G, SENT_D), wg_conv=np.full(G, SENT_U8, np.uint8), wg_nfev=np.full(G, SENT_I, np.int32),
+                 wg_grid_list=np.full(G, SENT_I, np.int32))
+        fn = lib().du_alpha_wg
+        fn.argtypes = common_in + [pd, pi, pd, pd, C.c_int] + tail + [pd, pu, pi, pi, pi]
+        fn.restype = C.c_int
+        rc = fn(_p(y, C.c_int32), N, N, G, _p(lst, C.c_int32), n_list, _p(cf, C.c_double), _p(sf, C.c_double),
+                _p(co, C.c_int32), _p(xc, C.c_double), _p(xx, C.c_double), P, *scal, *common, _p(o["wg_alpha"], C.c_double),
+                _p(o["wg_conv"], C.c_uint8), _p(o["wg_nfev"], C.c_int32), _p(o["wg_grid_list"], C.c_int32), C.byref(wgc))
+    _check(rc, f"{entry}({route}, P={P}, C={nc}, N={N}, eval_cap={eval_cap})")
+    o["nll_const"] = nl
+    o["grid_count"], o["park_count"] = int(gc.value), int(pc.value)
+    o["grid"] = o["grid_list"][:max(0, min(G, gc.value))]
+    o["parked"] = o["park_list"][:max(0, min(G, pc.value))]
+    o["state"] = {**{k: sd[:, i] for i, k in enumerate(STATE_D)}, **{k: si[:, i] for i, k in enumerate(STATE_I)}}
+    if entry != "du_rows_trace":
+        o["wg_grid_count"] = int(wgc.value)
+        o["wg_grid"] = o["wg_grid_list"][:max(0, min(G, wgc.value))]
+    return o
+
+
+def rows_trace(route, y, sf, cell_of, Xc, alpha_hat, min_disp, max_disp, min_mu, coef=None, cell_mu=None, genes=None,
+               prior_var=1.0, prior_reg=False, const_mode=CONST_COMPUTE, eval_cap=0, nll_const=None):
+    """One launch of k_alpha_rows (route "rows": P = C <= 4) or k_alpha_rows_c ("coef" / "cell_mu") with its own zeroed
+    queue and counters; eval_cap = 0 runs every fit to its end.  y: [G][N]; genes: the list (default: all, in order).
+    Returns a dict: alpha, conv, nfev, grid_list, park_list [G] (SENT_* where the kernel did not write), nll_const [G],
+    grid / parked (the lists up to their counts), grid_count, park_count and state: per field of the parked genes'
+    Lbfgsb1d (STATE_D, STATE_I) an array [G]."""
+    return _rows_launch("du_rows_trace", route, y, sf, cell_of, Xc, alpha_hat, min_disp, max_disp, min_mu, coef, cell_mu,
+                        genes, prior_var, prior_reg, const_mode, eval_cap, nll_const)
+
+
+def alpha_wg(y, sf, cell_of, Xc, alpha_hat, min_disp, max_disp, min_mu, coef, eval_cap, genes=None, prior_var=1.0,
+             prior_reg=False, const_mode=CONST_STORE, nll_const=None):
+    """rows_trace("rows", ..., eval_cap >= 1) with the constants stored (or loaded), then k_alpha_wg on the parked
+    states.  The dict of rows_trace for the row launch, and wg_alpha, wg_conv, wg_nfev, wg_grid_list [G], wg_grid,
+    wg_grid_count: what k_alpha_wg wrote."""
+    return _rows_launch("du_alpha_wg", "rows", y, sf, cell_of, Xc, alpha_hat, min_disp, max_disp, min_mu, coef, None,
+                        genes, prior_var, prior_reg, const_mode, eval_cap, nll_const)

@@ -12,10 +12,15 @@ SRC = os.path.join(HERE, "devunit.hip")  # dsq_math.h, dsq_wave.h
 SRC_LINALG = os.path.join(HERE, "devunit_linalg.hip")  # dsq_wide.h, dsq_wider.h, row_chol_solve
 SRC_STATS = os.path.join(HERE, "devunit_stats.hip")  # dsq_stats.h, dsq_lds_sort.h
 SRC_OPTIM = os.path.join(HERE, "devunit_optim.hip")  # dsq_lbfgsb_wave.h, dsq_lbfgsb.h, dsq_lbfgsb_par.h
-SRCS = [SRC, SRC_LINALG, SRC_STATS, SRC_OPTIM]
+SRC_ALPHA = os.path.join(HERE, "devunit_alpha.hip")  # dsq_alpha.h; launches the two row-kernel units below
+INC = os.path.join(ROOT, "pydeseq2_amd", "csrc")
+# the product's row kernels of the dispersion fit, unchanged and with the product's flags: devunit_alpha.hip calls their
+# launch_* entry points (dsq_launch.h)
+SRC_ROWS = os.path.join(INC, "dsq_k_alpha_rows.hip")
+SRC_ROWSC = os.path.join(INC, "dsq_k_alpha_rowsc.hip")
+SRCS = [SRC, SRC_LINALG, SRC_STATS, SRC_OPTIM, SRC_ALPHA, SRC_ROWS, SRC_ROWSC]
 HOST_H = os.path.join(HERE, "devunit_host.h")
 OUT = os.path.join(HERE, "_devunit.so")
-INC = os.path.join(ROOT, "pydeseq2_amd", "csrc")
 MAKEFILE = os.path.join(INC, "Makefile")
 HIPCC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
 
@@ -50,7 +55,7 @@ def asm_cmd(out):
     """Device assembly of the library: shows which branches of the headers the device build took.  One output file
     takes one input, so the other units are read in front of the first (-include); their names do not collide."""
     return [HIPCC, *cxxflags(), "--cuda-device-only", "-S", "-I", INC, "--include=" + SRC_LINALG, "--include=" + SRC_STATS,
-            "--include=" + SRC_OPTIM, SRC, "-o", out]
+            "--include=" + SRC_OPTIM, "--include=" + SRC_ALPHA, SRC, "-o", out]
 
 
 def build(force=False):

@@ -40,6 +40,19 @@ def test_flags_are_the_makefiles():
     assert dub.asm_cmd("x.s")[1:1 + len(flags)] == flags
 
 
+def test_sources_are_the_five_units_and_the_two_row_kernel_units_of_the_product():
+    """devunit_alpha.hip launches the product's row kernels: their two units are compiled into the library from csrc/
+    itself, with the same flags, and stay out of the assembly listing (which shows the branches the HEADERS took)."""
+    rel = [os.path.relpath(p, dub.ROOT) for p in dub.SRCS]
+    assert rel == ["tests/devunit/devunit.hip", "tests/devunit/devunit_linalg.hip", "tests/devunit/devunit_stats.hip",
+                   "tests/devunit/devunit_optim.hip", "tests/devunit/devunit_alpha.hip",
+                   "pydeseq2_amd/csrc/dsq_k_alpha_rows.hip", "pydeseq2_amd/csrc/dsq_k_alpha_rowsc.hip"]
+    assert all(os.path.exists(p) for p in dub.SRCS)
+    cmd, asm = dub.compile_cmd(), dub.asm_cmd("x.s")
+    assert all(p in cmd for p in dub.SRCS)
+    assert "--include=" + dub.SRC_ALPHA in asm and not any("dsq_k_alpha_rows" in c for c in asm)
+
+
 @needs_hipcc
 def test_builds():
     out = dub.build()
