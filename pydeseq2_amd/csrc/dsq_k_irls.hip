@@ -20,25 +20,6 @@ __device__ unsigned long long g_phase_total_irls[16];
 #endif
 constexpr int irls_min_waves(int p) { return p <= 2 ? DSQ_IRLS_WAVES_P2 : (p <= 5 ? 1 : 2); }
 
-// fused outputs of one gene (lane 0 writes)
-template <int P>
-__device__ __forceinline__ void epilogue_begin(LfcEpilogue& E, const IrlsExtras& ex, int g, int ldn) {
-    if (ex.flags != nullptr) {
-        E.flags = ex.flags; E.robust_disp = ex.robust_disp[g]; E.cutoff = ex.cutoff;
-        E.cooks_row = ex.cooks ? ex.cooks + (size_t)g * ldn : nullptr;
-    }
-    if (ex.ridge != nullptr) { E.ridge = ex.ridge; E.contrast = ex.contrast; E.lfc_null = ex.lfc_null; E.alt = ex.alt; }
-}
-__device__ __forceinline__ void epilogue_store(const LfcEpilogue& E, const IrlsExtras& ex, int g) {
-    if (ex.flags != nullptr) {
-        ex.any_all[g] = (uint8_t)E.cooks.any_gt_all;
-        ex.any_use[g] = (uint8_t)E.cooks.any_gt_use;
-        ex.any_use_nr[g] = (uint8_t)E.cooks.any_gt_use_nr;
-        ex.few_above[g] = (uint8_t)E.cooks.few_above;
-    }
-    if (ex.ridge != nullptr) { ex.pvals[g] = E.wald.p; ex.stats[g] = E.wald.stat; ex.se[g] = E.wald.se; }
-}
-
 template <int P, int CELL>
 __global__ __launch_bounds__(kBlock, CELL == 1 ? cell_min_waves(P) : irls_min_waves(P)) void k_irls(const int32_t* __restrict__ y, int ldn,
                                                  const double* __restrict__ sf, const double* __restrict__ lsf,
@@ -114,7 +95,7 @@ __global__ __launch_bounds__(kBlock, CELL == 1 ? cell_min_waves(P) : irls_min_wa
     A.max_beta = max_beta; A.maxiter = maxiter; A.full_rank = full_rank != 0;
     if (CELL) { A.cells = &ex.cells; A.cell_ws = CELL == 1 ? (void*)&cellw[w] : nullptr; }
     LfcEpilogue E;
-    epilogue_begin<P>(E, ex, g, ldn);
+    epilogue_begin(E, ex, g, ldn);
     double b[P];
     const IrlsOut o = irls_gene<DeviceWave, P, CELL>(A, b, mu ? mu + (size_t)g * ldn : nullptr,
                                                      hat ? hat + (size_t)g * ldn : nullptr, &E);
@@ -210,7 +191,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_irls_row(const int32_t* __restric
     }
 #endif
     LfcEpilogue E;
-    epilogue_begin<P>(E, ex, g, ldn);
+    epilogue_begin(E, ex, g, ldn);
     double b[P];
     const IrlsOut o = irls_gene<RowWave, P, 1>(A, b, mu ? mu + (size_t)g * ldn : nullptr,
                                                hat ? hat + (size_t)g * ldn : nullptr, &E);
@@ -335,7 +316,7 @@ __global__ __launch_bounds__(kBlock) void k_irls_rescue(const int32_t* __restric
     A.max_beta = max_beta; A.maxiter = maxiter; A.full_rank = full_rank != 0;
     __shared__ IrlsRescueWork<P> work[kWavesPerBlock];
     LfcEpilogue E;
-    epilogue_begin<P>(E, ex, g, ldn);
+    epilogue_begin(E, ex, g, ldn);
     // slot-ordered Cook's layer (mixed designs): this kernel writes sample order - into the scratch row of list entry k
     if (ex.cooks_ld != 0 && E.cooks_row != nullptr) E.cooks_row = ex.cooks_tmp + (size_t)k * ldn;
     double b[P];

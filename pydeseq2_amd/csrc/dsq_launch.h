@@ -6,6 +6,8 @@
 #include <cstdint>
 
 #include "../../include/deseq_hip.h"
+// LfcEpilogue, for epilogue_begin / epilogue_store next to IrlsExtras (templates only: no code in the other units)
+#include "dsq_irls.h"
 #include "dsq_linalg.h"
 #include "dsq_mix.h"
 
@@ -36,7 +38,8 @@ inline int current_device_cus() {
 #endif
 constexpr int cell_min_waves(int p) { return p <= 6 ? 3 : DSQ_CELL_WAVES_WIDE; }
 
-// ---- dsq_k_wide.hip: run-time-P kernels (LDS matrices, matrix-core Gram accumulation), P <= 48; P > 48 forwarded to dsq_k_wider.hip
+// ---- dsq_k_wide.hip: run-time-P kernels (matrix-core Gram accumulation): LDS matrices for P <= 48, matrices in
+// device-memory slots for P = 49 ... 128; each entry point picks the geometry by P
 int wide_min_p();
 bool wide_with_cells();  // DSQ_WIDE_CELLS=1 (measurements): designs with cells may take the LDS path as well
   // designs at least this wide take them (default: DSQ_REG_MAX_P + 1)
@@ -71,40 +74,9 @@ hipError_t launch_wide_wald(hipStream_t st, const double* mu, int ldn, const dou
                             int N, int G, int P, const double* disp, const double* beta, const double* d_ridge,
                             const double* d_contrast, double lfc_null, int alt, double* pvals, double* stats,
                             double* se);
-// ---- dsq_k_wider.hip: designs of 49 ... 128 columns (device-memory matrices; launch_wide_* forward P > 48 here)
-// Their slots are kept per (device, stream) and grown on demand; the owner of a stream releases them before it
-// destroys the stream (dsq_destroy).
+// The slots of the designs of 49 ... 128 columns are kept per (device, stream) and grown on demand; the owner of a
+// stream releases them before it destroys the stream (dsq_destroy).
 void wider_release(hipStream_t st);
-hipError_t launch_wider_mom(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* Xt,
-                            const double* pinvXt, int ldx, int N, int G, int P, double min_disp, double max_disp,
-                            double min_mu, double* normed_mean, double* rough, double* moments, double* mom,
-                            double* mu, double* coef, const double* d_s_mean_inv);
-hipError_t launch_wider_rough_normed(hipStream_t st, const double* normed, int ldn, const double* Xt,
-                                     const double* pinvXt, int ldx, int N, int G, int P, double* out);
-hipError_t launch_wider_alpha(hipStream_t st, const int32_t* y, const double* mu, int ldn, const double* Xt, int ldx,
-                              int N, int G, int P, const double* alpha_hat, double min_disp, double max_disp,
-                              double prior_var, int cr_reg, int prior_reg, double* alpha, uint8_t* conv,
-                              int32_t* nfev, double* nll_const, int const_mode);
-hipError_t launch_wider_alpha_grid(hipStream_t st, const int32_t* y, const double* mu, int ldn, const double* Xt,
-                                   int ldx, int N, int P, double min_disp, double max_disp, double* alpha,
-                                   const int32_t* list, int n_list);
-hipError_t launch_wider_irls(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* lsf,
-                             const double* Xt, const double* pinvXt, int ldx, int N, int G, int P, int full_rank,
-                             const double* disp, double min_mu, double beta_tol, double min_beta, double max_beta,
-                             int maxiter, double* beta, double* mu, double* hat, uint8_t* conv, int32_t* iters,
-                             int32_t* fb_count, int32_t* fb_list, const IrlsExtras* extras);
-hipError_t launch_wider_irls_rescue(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* lsf,
-                                    const double* Xt, const double* pinvXt, int ldx, int N, int P, int full_rank,
-                                    const double* disp, double min_mu, double beta_tol, double min_beta,
-                                    double max_beta, int maxiter, double* beta, double* mu, double* hat, uint8_t* conv,
-                                    int32_t* iters, const int32_t* fb_list, int n_fb, const IrlsExtras* extras);
-hipError_t launch_wider_irls_layers(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* Xt,
-                                    int ldx, int N, int G, int P, const double* disp, const double* beta, double min_mu,
-                                    double* mu, double* hat);
-hipError_t launch_wider_wald(hipStream_t st, const double* mu, int ldn, const double* sf, const double* Xt, int ldx,
-                             int N, int G, int P, const double* disp, const double* beta, const double* d_ridge,
-                             const double* d_contrast, double lfc_null, int alt, double* pvals, double* stats,
-                             double* se);
 
 // ---- dsq_k_alpha.hip
 // optional inputs of the dispersion kernel (zero-initialised = none)
@@ -251,6 +223,23 @@ struct IrlsExtras {
     int part_want;
     int part_shared_ready;
 };
+// fused outputs of one gene (lane 0 writes)
+__device__ __forceinline__ void epilogue_begin(LfcEpilogue& E, const IrlsExtras& ex, int g, int ldn) {
+    if (ex.flags != nullptr) {
+        E.flags = ex.flags; E.robust_disp = ex.robust_disp[g]; E.cutoff = ex.cutoff;
+        E.cooks_row = ex.cooks ? ex.cooks + (size_t)g * ldn : nullptr;
+    }
+    if (ex.ridge != nullptr) { E.ridge = ex.ridge; E.contrast = ex.contrast; E.lfc_null = ex.lfc_null; E.alt = ex.alt; }
+}
+__device__ __forceinline__ void epilogue_store(const LfcEpilogue& E, const IrlsExtras& ex, int g) {
+    if (ex.flags != nullptr) {
+        ex.any_all[g] = (uint8_t)E.cooks.any_gt_all;
+        ex.any_use[g] = (uint8_t)E.cooks.any_gt_use;
+        ex.any_use_nr[g] = (uint8_t)E.cooks.any_gt_use_nr;
+        ex.few_above[g] = (uint8_t)E.cooks.few_above;
+    }
+    if (ex.ridge != nullptr) { ex.pvals[g] = E.wald.p; ex.stats[g] = E.wald.stat; ex.se[g] = E.wald.se; }
+}
 // does launch_irls honour IrlsExtras::part for this design?  (the run-time-P LDS kernels do not)
 bool irls_takes_parts(int N, int P, int n_cells, const MixDesign* mix, int full_rank);
 bool irls_takes_mix(const MixDesign* mix, int full_rank);

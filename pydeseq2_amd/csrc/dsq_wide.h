@@ -475,7 +475,31 @@ DSQ_HD void alpha_eval_wide(const WideAlphaArgs& A, const WideWorkT<MP>& W, doub
     }
 }
 
-// fit_alpha_mle (utils.py:441-564) incl. the grid-search fallback (grid_search.py:54-142), any P
+// grid_fit_alpha (grid_search.py:54-142): 100 points on [lo, hi], then 100 around the best one; Cox-Reid term on, no
+// prior (the reference passes six positional arguments).  Returns the best log-alpha.
+template <class Wv, int MP>
+DSQ_HD double grid_alpha_wide(const WideAlphaArgs& A, const WideWorkT<MP>& W, double lo, double hi) {
+    double lohi[2] = {lo, hi};
+    double best_la = 0.0;
+    for (int level = 0; level < 2; ++level) {
+        double best = 0.0;
+        int kbest = 0;
+        bool best_nan = false;
+        for (int i = 0; i < 100; ++i) {
+            double f, gu;
+            alpha_eval_wide<Wv, false>(A, W, linspace_at(lohi[0], lohi[1], 100, i), true, false, f, gu);
+            const bool isn = (f != f);
+            if (i == 0 || (!best_nan && (isn || f < best))) { best = f; kbest = i; best_nan = isn; }
+        }
+        const double c = linspace_at(lohi[0], lohi[1], 100, kbest);
+        const double delta = linspace_at(lohi[0], lohi[1], 100, 1) - linspace_at(lohi[0], lohi[1], 100, 0);
+        best_la = c;
+        lohi[0] = c - delta; lohi[1] = c + delta;
+    }
+    return best_la;
+}
+
+// fit_alpha_mle (utils.py:441-564) incl. the grid-search fallback, any P
 template <class Wv, int MP>
 DSQ_HD AlphaOut fit_alpha_wide(const int32_t* y, const double* mu, const double* Xt, int ldx, int N,
                                const WideWorkT<MP>& W, const CellDesign* cells, double alpha_hat, double min_disp,
@@ -498,26 +522,7 @@ DSQ_HD AlphaOut fit_alpha_wide(const int32_t* y, const double* mu, const double*
     o.converged = m.success ? 1 : 0;
     o.nfev = m.nfev; o.nit = m.it; o.status = m.status;
     o.alpha = exp(m.x);
-    if (!m.success) {  // grid search: Cox-Reid term on, no prior (the reference passes six positional arguments)
-        double lohi[2] = {lo, hi};
-        double best_la = 0.0;
-        for (int level = 0; level < 2; ++level) {
-            double best = 0.0;
-            int kbest = 0;
-            bool best_nan = false;
-            for (int i = 0; i < 100; ++i) {
-                double f, gu;
-                alpha_eval_wide<Wv, false>(A, W, linspace_at(lohi[0], lohi[1], 100, i), true, false, f, gu);
-                const bool isn = (f != f);
-                if (i == 0 || (!best_nan && (isn || f < best))) { best = f; kbest = i; best_nan = isn; }
-            }
-            const double c = linspace_at(lohi[0], lohi[1], 100, kbest);
-            const double delta = linspace_at(lohi[0], lohi[1], 100, 1) - linspace_at(lohi[0], lohi[1], 100, 0);
-            best_la = c;
-            lohi[0] = c - delta; lohi[1] = c + delta;
-        }
-        o.alpha = exp(best_la);
-    }
+    if (!m.success) o.alpha = exp(grid_alpha_wide<Wv>(A, W, lo, hi));
     return o;
 }
 

@@ -3,7 +3,7 @@
 // Five p x p matrices of a gene take 660 KB at p = 128: more than a CU's 160 KB of LDS.  This family runs the very
 // templates of dsq_wide.h (same formulas, same optimisers, same per-entry operation order of the Cholesky / inverse /
 // solves) over WiderWork = WideWorkT<128>, bound with bind_split:
-//   * device memory, one slot per resident workgroup (dsq_k_wider.hip): the Gram tile accumulators `gacc` and the five
+//   * device memory, one slot per resident workgroup (SlotGeom, dsq_k_wide.hip): the Gram tile accumulators `gacc` and the five
 //     p x p matrices M, dM, L, L^-1, inverse;
 //   * LDS: the staged design chunk xs (rows x 65), the chunk's weights and the small vectors (8 x 128).
 // The Gram matrices are still built by v_mfma_f64_16x16x4_f64 on 16 x 16 lower-triangle tiles (up to 36 per matrix),

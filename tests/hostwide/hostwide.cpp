@@ -10,7 +10,7 @@
 using namespace dsq;
 
 namespace {
-// a gene's workspace: LDS part and device-memory slot, as dsq_k_wider.hip binds them
+// a gene's workspace: LDS part and device-memory slot, as SlotGeom (dsq_k_wide.hip) binds them
 struct HostSlot {
     std::vector<double> lds, mem;
     WiderWork W;

@@ -1,5 +1,5 @@
-"""Designs of 49 ... 128 columns on the GPU (dsq_k_wider.hip: p x p matrices in device-memory slots, one gene per
-workgroup): the reference KATs through the plug-in C ABI, deseq2() + Wald end to end against the oracle (the paired
+"""Designs of 49 ... 128 columns on the GPU (the slot geometry of dsq_k_wide.hip: p x p matrices in device-memory slots, one
+gene per workgroup): the reference KATs through the plug-in C ABI, deseq2() + Wald end to end against the oracle (the paired
 `~subject + condition` design, a 72-level factor with outliers, 128 mixed columns), the façade, run-to-run bit equality
 and two ranks sharing the genes."""
 import threading
@@ -251,8 +251,8 @@ def test_paired_design_two_ranks_threads(paired):
 
 
 def test_irls_rescue_kernel_reuses_its_workspace_across_genes():
-    """maxiter = 2 sends every gene through the L-BFGS-B rescue (utils.py:374-413), k_irls_rescue_wider.  600 genes are
-    more than the resident workgroups, so later genes run on workgroups (LDS optimiser state, device-memory slot) that
+    """maxiter = 2 sends every gene through the L-BFGS-B rescue (utils.py:374-413), k_irls_rescue_wide<SlotGeom>.  600 genes
+    are more than the resident workgroups, so later genes run on workgroups (LDS optimiser state, device-memory slot) that
     fitted an earlier gene: against the oracle at both ends, and bitwise equal to the same genes fitted alone."""
     from pydeseq2_amd import HipInference
 

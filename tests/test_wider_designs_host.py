@@ -71,8 +71,9 @@ def test_paired_design_of_64_subjects_builds_65_columns_without_the_gpu():
 
 @pytest.mark.parametrize("case", ["p65", "p72", "p128"])
 def test_wider_templates_vs_reference_kats(case):
-    """dsq_wide.h over WiderWork (matrices bound apart from the LDS part, as dsq_k_wider.hip binds them) against the
-    reference, at the tolerances of the 13 ... 48-column KATs (test_hostsim.py::test_wide_path_vs_reference_kats)."""
+    """dsq_wide.h over WiderWork (matrices bound apart from the LDS part, as SlotGeom of dsq_k_wide.hip binds them)
+    against the reference, at the tolerances of the 13 ... 48-column KATs
+    (test_hostsim.py::test_wide_path_vs_reference_kats)."""
     k = load_kat(case)
     counts, X, sf = k["counts"], k["X"], k["sf"]
     N, P = X.shape
