@@ -473,6 +473,14 @@ int dsq_dev_wald(dsq_ctx* ctx, const double* d_mu, int ldn, const double* d_sf, 
                  int ldx, int N, int G, int P, const double* d_disp, const double* d_beta,
                  const double* h_ridge, const double* h_contrast, double lfc_null, int alt,
                  double* d_pvals, double* d_stats, double* d_se);
+/* dsq_dev_wald for K contrasts of the same fit in one launch: per gene X^T W X is accumulated and M + ridge factored
+ * once, only the per-contrast tail (two triangular solves, the quadratic form, the alternative hypothesis) repeats.
+ * d_contrasts: [K][P] in DEVICE memory (K >= 1, no upper limit); h_ridge: [P*P] host; the outputs are [G][K] (a gene's K
+ * results are consecutive).  d_mu may be null as for dsq_dev_wald. */
+int dsq_dev_wald_multi(dsq_ctx* ctx, const double* d_mu, int ldn, const double* d_sf, const double* d_Xt, int ldx,
+                       int N, int G, int P, const double* d_disp, const double* d_beta, const double* h_ridge,
+                       const double* d_contrasts, int K, double lfc_null, int alt, double* d_pvals, double* d_stats,
+                       double* d_se);
 /* Likelihood-ratio test of a nested reduced design (DESeq2's nbinomLRT; csrc/dsq_lrt.h): per gene
  *   stat = 2 sum_n [ y (eta_f - eta_r) - (y + 1/disp) (log(1/disp + mu_f) - log(1/disp + mu_r)) ],  mu = sf exp(X beta)
  * from the coefficients of the two fits (d_beta [G][P], d_beta_reduced [G][P_reduced], both at the dispersions d_disp),

@@ -207,6 +207,8 @@ def load():
     proto("dsq_dev_replace_outliers2", _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_int, c_int, c_double, _vp, _vp, c_int, _vp)
     proto("dsq_dev_wald", _vp, _vp, c_int, _vp, _vp, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp,
           c_double, c_int, _vp, _vp, _vp)
+    proto("dsq_dev_wald_multi", _vp, _vp, c_int, _vp, _vp, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp, c_int,
+          c_double, c_int, _vp, _vp, _vp)
     proto("dsq_dev_lrt", _vp, _vp, c_int, _vp, _vp, c_int, c_int, _vp, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp, _vp)
     proto("dsq_dev_chisq_sf", _vp, _vp, c_int, c_int, _vp)
     proto("dsq_dev_gather_rows_f64", _vp, _vp, c_int, _vp, c_int, c_int, _vp)
@@ -246,7 +248,7 @@ EXPORTS = [
     "dsq_plugin_digest_host", "dsq_comm_info", "dsq_host_sync_count", "dsq_dev_pack2", "dsq_dev_unzip2",
     "dsq_mix_bind", "dsq_mix_bind2", "dsq_dev_mix_counts_to_slots", "dsq_dev_mix_mu_slots",
     "dsq_lfc_fork_begin", "dsq_lfc_fork_end", "dsq_lfc_set_part", "dsq_lfc_takes_parts", "dsq_dev_select_dispersions_part", "dsq_lfc_prepare", "dsq_alpha_set_late_flags",
-    "dsq_dev_lrt", "dsq_dev_chisq_sf",
+    "dsq_dev_lrt", "dsq_dev_chisq_sf", "dsq_dev_wald_multi",
 ]
 
 

@@ -852,6 +852,17 @@ def reduced_design_matrix(dds, reduced) -> pd.DataFrame:
     return Xr.set_axis(dds.obs_names, axis=0)
 
 
+def pairwise_contrasts(dds, factor) -> list:
+    """Every pairwise comparison ``[factor, b, a]`` (a < b) of the levels of ``factor``, in the level order
+    ``DeseqStats`` resolves contrasts with - the sorted levels as strings: (l1, l0), (l2, l0), ..., (l2, l1), ...  Reads
+    ``dds.obs`` only (no GPU); for ``DeseqStats.batch``."""
+    factor = str(factor)
+    if factor not in dds.obs.columns:
+        raise ValueError(f"The contrast variable ('{factor}') should be one of the design factors.")
+    levels = sorted(dds.obs[factor].astype(str).unique())
+    return [[factor, levels[j], levels[i]] for i in range(len(levels)) for j in range(i + 1, len(levels))]
+
+
 class DeseqStats:
     """Wald tests, adjusted p-values and LFC shrinkage (cf. ``pydeseq2.ds.DeseqStats``, ds.py:110-447).
 
@@ -915,16 +926,46 @@ class DeseqStats:
                 v[cols.index(name)] = sign
         return v
 
+    def _ridge(self):
+        P = self.LFC.shape[1]
+        if self.prior_LFC_var is not None:  # ds.py:326-329
+            return np.diag(1.0 / np.asarray(self.prior_LFC_var, dtype=float) ** 2)
+        return np.diag(np.repeat(1e-6, P))
+
+    @classmethod
+    def batch(cls, dds: DeseqDataSet, contrasts, **kwargs) -> list:
+        """Wald tests of many contrasts of the same fit: ``[DeseqStats(dds, c, **kwargs) for c in contrasts]`` with the
+        Wald statistics of all of them computed by ONE launch (``DeseqPipeline.wald_multi``: the Gram matrix and its
+        factor once per gene, one upload, one download) instead of one per contrast.  Each entry of ``contrasts`` is
+        what ``DeseqStats(contrast=...)`` takes - a ``[factor, tested, ref]`` list or a vector, mixed freely; see
+        ``pairwise_contrasts``.  ``kwargs``: ``alpha``, ``cooks_filter``, ``independent_filter``, ``prior_LFC_var``,
+        ``lfc_null``, ``alt_hypothesis``, ``quiet``.  The objects come back in the order given with ``p_values``,
+        ``statistics`` and ``SE`` filled, so ``summary()`` goes straight to the filters and BH; ``summary(lfc_null=...)``
+        with other values, ``lfc_shrink`` etc. behave as on any other ``DeseqStats`` (the single-contrast path).
+        A bad contrast raises what ``DeseqStats(...)`` raises for it, before anything is launched.  The likelihood-ratio
+        statistic does not depend on the contrast: ``test="LRT"`` is refused.  Single process only: the distributed
+        pipeline has no multi-contrast launch."""
+        if kwargs.get("test", "wald") != "wald" or kwargs.get("reduced") is not None:
+            raise ValueError("DeseqStats.batch() runs Wald tests: the likelihood-ratio statistic does not depend on the "
+                             "contrast (use DeseqStats(dds, contrast, test='LRT', reduced=...) once).")
+        contrasts = list(contrasts)
+        if not contrasts:
+            raise ValueError("DeseqStats.batch() needs at least one contrast.")
+        out = [cls(dds, c, **kwargs) for c in contrasts]
+        first = out[0]
+        pv, st, se = dds._pipe.wald_multi(dds._res, np.stack([o.contrast_vector for o in out]), first.lfc_null,
+                                          first.alt_hypothesis, lfc=first.LFC.to_numpy(), ridge=first._ridge())
+        idx = dds.var_names
+        for k, o in enumerate(out):
+            o.p_values, o.statistics, o.SE = (pd.Series(v[k], index=idx) for v in (pv, st, se))
+            o._wald_key = (o.lfc_null, o.alt_hypothesis)
+        return out
+
     def run_wald_test(self):
         """Wald test of the CURRENT coefficients (``self.LFC``: shrunk ones after ``lfc_shrink``), ds.py:303-360."""
         r = self.dds._res
-        P = self.LFC.shape[1]
-        if self.prior_LFC_var is not None:  # ds.py:326-329
-            ridge = np.diag(1.0 / np.asarray(self.prior_LFC_var, dtype=float) ** 2)
-        else:
-            ridge = np.diag(np.repeat(1e-6, P))
         pv, st, se = self.dds._pipe.wald(r, self.contrast_vector, self.lfc_null, self.alt_hypothesis,
-                                         lfc=self.LFC.to_numpy(), ridge=ridge)
+                                         lfc=self.LFC.to_numpy(), ridge=self._ridge())
         idx = self.dds.var_names
         self.p_values, self.statistics, self.SE = pd.Series(pv, index=idx), pd.Series(st, index=idx), pd.Series(se, index=idx)
         self._wald_key = (self.lfc_null, self.alt_hypothesis)

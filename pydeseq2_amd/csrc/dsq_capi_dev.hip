@@ -593,6 +593,24 @@ int dsq_dev_wald(dsq_ctx* ctx, const double* d_mu, int ldn, const double* d_sf, 
     return DSQ_OK;
 }
 
+int dsq_dev_wald_multi(dsq_ctx* ctx, const double* d_mu, int ldn, const double* d_sf, const double* d_Xt, int ldx,
+                       int N, int G, int P, const double* d_disp, const double* d_beta, const double* h_ridge,
+                       const double* d_contrasts, int K, double lfc_null, int alt, double* d_pvals, double* d_stats,
+                       double* d_se) {
+    DSQ_CHECK_ARG(P >= 1 && P <= DSQ_MAX_P, "P out of range");
+    DSQ_CHECK_ARG(alt >= 0 && alt <= 4, "unknown alternative hypothesis");
+    DSQ_CHECK_ARG(K >= 1, "K: at least one contrast");
+    DSQ_CHECK_ARG(d_contrasts != nullptr, "d_contrasts: K x P contrasts in device memory");
+    double* d_ridge;
+    double* h_unused;
+    { const int rc = ridge_stage(ctx, P, &d_ridge, &h_unused); if (rc != DSQ_OK) return fail(ctx, rc, "ridge staging: out of memory"); }
+    DSQ_HIP(hipMemcpyAsync(d_ridge, h_ridge, (size_t)P * P * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    DSQ_HIP(hipStreamSynchronize(ctx->stream));
+    DSQ_HIP(dsq::launch_wald_multi(ctx->stream, d_mu, ldn, d_sf, d_Xt, ldx, N, G, P, d_disp, d_beta, d_ridge, d_contrasts,
+                                   K, lfc_null, alt, d_pvals, d_stats, d_se));
+    return DSQ_OK;
+}
+
 int dsq_dev_lrt(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, const double* d_Xt, int ldx, int P,
                 const double* d_Xt_reduced, int ldx_reduced, int P_reduced, int N, int G, const double* d_disp,
                 const double* d_beta, const double* d_beta_reduced, double* d_stats, double* d_pvals) {

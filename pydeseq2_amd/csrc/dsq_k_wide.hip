@@ -594,6 +594,42 @@ hipError_t launch_wide_wald(hipStream_t st, const double* mu, int ldn, const dou
     return P > kWideMaxP ? go(SlotGeom{}) : go(LdsGeom{});
 }
 
+// K contrasts ([K][P]) of one fit: one Gram matrix and one factorisation per gene, the tail per contrast; results [G][K]
+template <class Geo>
+__global__ __launch_bounds__(Geo::kThreads) void k_wald_multi_wide(const double* __restrict__ mu, int ldn,
+                                                                   const double* __restrict__ sf,
+                                                                   const double* __restrict__ Xt, int ldx, int N, int G,
+                                                                   int P, const double* __restrict__ disp,
+                                                                   const double* __restrict__ beta,
+                                                                   const double* __restrict__ ridge,
+                                                                   const double* __restrict__ contrasts, int K,
+                                                                   double lfc_null, int alt, double* __restrict__ pvals,
+                                                                   double* __restrict__ stats, double* __restrict__ se,
+                                                                   Geo geo) {
+    using Wv = typename Geo::Wave;
+    const typename Geo::Work W = geo.work(P);
+    geo.each(G, [&](int g) {
+        for (int j = Wv::lane(); j < P; j += 64) W.v(0)[j] = beta[(size_t)g * P + j];
+        Wv::sync();
+        const size_t o = (size_t)g * K;
+        wald_gene_multi_wide<Wv>(mu ? mu + (size_t)g * ldn : nullptr, sf, Xt, ldx, N, disp[g], W, ridge, contrasts, K,
+                                 lfc_null, alt, Geo::lane0(), pvals + o, stats + o, se + o);
+    });
+}
+
+hipError_t launch_wide_wald_multi(hipStream_t st, const double* mu, int ldn, const double* sf, const double* Xt, int ldx,
+                                  int N, int G, int P, const double* disp, const double* beta, const double* d_ridge,
+                                  const double* d_contrasts, int K, double lfc_null, int alt, double* pvals,
+                                  double* stats, double* se) {
+    if (G <= 0) return hipSuccess;
+    if (K < 1) return hipErrorInvalidValue;
+    const auto go = [&](auto geo) {
+        return wide_run(geo, k_wald_multi_wide<decltype(geo)>, st, P, G, 0, LdsGeom::kWaves, mu, ldn, sf, Xt, ldx, N, G,
+                        P, disp, beta, d_ridge, d_contrasts, K, lfc_null, alt, pvals, stats, se);
+    };
+    return P > kWideMaxP ? go(SlotGeom{}) : go(LdsGeom{});
+}
+
 // the width from which the register / cell kernels hand over to this path (DSQ_WIDE_MIN_P: measurements)
 int wide_min_p() {
     static const int v = [] {

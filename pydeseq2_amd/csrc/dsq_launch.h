@@ -74,6 +74,10 @@ hipError_t launch_wide_wald(hipStream_t st, const double* mu, int ldn, const dou
                             int N, int G, int P, const double* disp, const double* beta, const double* d_ridge,
                             const double* d_contrast, double lfc_null, int alt, double* pvals, double* stats,
                             double* se);
+hipError_t launch_wide_wald_multi(hipStream_t st, const double* mu, int ldn, const double* sf, const double* Xt, int ldx,
+                                  int N, int G, int P, const double* disp, const double* beta, const double* d_ridge,
+                                  const double* d_contrasts, int K, double lfc_null, int alt, double* pvals,
+                                  double* stats, double* se);
 // The slots of the designs of 49 ... 128 columns are kept per (device, stream) and grown on demand; the owner of a
 // stream releases them before it destroys the stream (dsq_destroy).
 void wider_release(hipStream_t st);
@@ -310,6 +314,12 @@ hipError_t launch_wald(hipStream_t st, const double* mu, int ldn, const double* 
                        int ldx, int N, int G, int P, const double* disp, const double* beta,
                        const double* d_ridge, const double* d_contrast, double lfc_null, int alt,
                        double* pvals, double* stats, double* se);
+// ---- dsq_k_wald_multi.hip: K contrasts (d_contrasts [K][P]) of one fit, X^T W X and its factor once per gene; results
+// [G][K]; designs wider than DSQ_REG_MAX_P columns go to launch_wide_wald_multi
+hipError_t launch_wald_multi(hipStream_t st, const double* mu, int ldn, const double* sf, const double* Xt, int ldx,
+                             int N, int G, int P, const double* disp, const double* beta, const double* d_ridge,
+                             const double* d_contrasts, int K, double lfc_null, int alt, double* pvals, double* stats,
+                             double* se);
 // ---- dsq_k_lrt.hip: likelihood-ratio statistic of a reduced design (Xr: its transposed design, 1 <= Pr < Pf) and the
 // chi-square survival function with integer degrees of freedom
 hipError_t launch_lrt(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* Xf, int ldf, int Pf,

@@ -346,6 +346,107 @@ DSQ_HD WaldOut wald_gene(const double* mu, const double* sf, const double* Xt, i
     return wald_from_M<P>(M, beta, ridge, contrast, lfc_null, alt);
 }
 
+// ---- many contrasts of one fit: wald_from_M split into what does not depend on the contrast (the Cholesky factor of
+// M + ridge) and the per-contrast tail.  Same operations in the same order as wald_from_M; wald_from_M itself (which
+// also serves the fused LFC epilogues) is left as it is.
+template <int P>
+DSQ_HD void wald_factor(const double (&M)[Tri<P>::N], const double* ridge /*[P*P]*/, double (&Hm)[Tri<P>::N]) {
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) Hm[tri(i, j)] = M[tri(i, j)] + ridge[i * P + j];
+    }
+    chol<P>(Hm);
+}
+
+// Hm: the factor wald_factor left
+template <int P>
+DSQ_HD WaldOut wald_tail(const double (&M)[Tri<P>::N], const double (&Hm)[Tri<P>::N], const double (&beta)[P],
+                         const double* contrast /*[P]*/, double lfc_null, int alt) {
+    // (a lane's own contrast: it is read again where the tail needs it instead of being held across the solves)
+    double Hc[P], MHc[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) Hc[j] = contrast[j];
+    chol_solve<P>(Hm, Hc);                   // H c
+    sym_matvec<P>(M, Hc, MHc);
+    double q = 0.0;
+#pragma unroll
+    for (int j = 0; j < P; ++j) q += Hc[j] * MHc[j];
+    WaldOut o;
+    o.se = sqrt(q);
+    double stat = 0.0, pval;
+    if (alt == ALT_NONE) {
+        double t = 0.0;
+#pragma unroll
+        for (int j = 0; j < P; ++j) t += contrast[j] * (beta[j] - lfc_null);
+        stat = t / o.se;
+        pval = 2.0 * norm_sf(fabs(stat));
+    } else if (alt == ALT_GREATER) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) stat += contrast[j] * np_fmax((beta[j] - lfc_null) / o.se, 0.0);
+        pval = norm_sf(stat);
+    } else if (alt == ALT_LESS) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) stat += contrast[j] * np_fmin((beta[j] - lfc_null) / o.se, 0.0);
+        pval = norm_sf(fabs(stat));
+    } else if (alt == ALT_GREATER_ABS) {
+#pragma unroll
+        for (int j = 0; j < P; ++j)
+            stat += contrast[j] * (dsign(beta[j]) * np_fmax((fabs(beta[j]) - lfc_null) / o.se, 0.0));
+        pval = 2.0 * norm_sf(fabs(stat));
+    } else {  // lessAbs: greater(-|null|) vs less(|null|)
+        const double an = fabs(lfc_null);
+        double sa = 0.0, sb = 0.0;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            sa += contrast[j] * np_fmax((beta[j] + an) / o.se, 0.0);
+            sb += contrast[j] * np_fmin((beta[j] - an) / o.se, 0.0);
+        }
+        const double pa = norm_sf(sa), pb = norm_sf(fabs(sb));
+        stat = (fabs(sb) < fabs(sa)) ? sb : sa;
+        pval = (pb > pa) ? pb : pa;
+    }
+    o.stat = stat;
+    o.p = pval;
+    return o;
+}
+
+// K contrasts ([K][P]) of one gene: M is accumulated once, by the loop of wald_gene (same additions in the same
+// order); after sum_n every lane holds it and factors M + ridge once; then lane l takes the contrasts l, l + W, ...
+// pvals / stats / se: the gene's K results each (consecutive lanes write consecutive entries).
+template <class Wv, int P>
+DSQ_HD void wald_gene_multi(const double* mu, const double* sf, const double* Xt, int ldx, int N, double disp,
+                            const double (&beta)[P], const double* ridge /*[P*P]*/, const double* contrasts, int K,
+                            double lfc_null, int alt, double* pvals, double* stats, double* se) {
+    constexpr int T = Tri<P>::N;
+    double M[T], Hm[T];
+#pragma unroll
+    for (int k = 0; k < T; ++k) M[k] = 0.0;
+    for (int n = Wv::lane(); n < N; n += Wv::W) {
+        double x[P];
+        double eta = 0.0;
+#pragma unroll
+        for (int j = 0; j < P; ++j) { x[j] = Xt[j * ldx + n]; eta += x[j] * beta[j]; }
+        const double m = (mu != nullptr) ? mu[n] : sf[n] * exp(eta);
+        const double w = m / (1.0 + m * disp);
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            const double xw = x[i] * w;
+#pragma unroll
+            for (int j = 0; j <= i; ++j) M[tri(i, j)] += xw * x[j];
+        }
+    }
+    Wv::template sum_n<T>(M);
+    wald_factor<P>(M, ridge, Hm);
+#pragma nounroll
+    for (int k = Wv::lane(); k < K; k += Wv::W) {
+        const WaldOut o = wald_tail<P>(M, Hm, beta, contrasts + (size_t)k * P, lfc_null, alt);
+        pvals[k] = o.p;
+        stats[k] = o.stat;
+        se[k] = o.se;
+    }
+}
+
 // ---------------------------------------------------------------- Cook's distances
 struct CellPlan {
     // samples grouped by design cell; only cells with >= 3 replicates are listed.

@@ -980,4 +980,116 @@ DSQ_HD WaldOut wald_gene_wide(const double* mu, const double* sf, const double* 
     return wald_wide<Wv>(W, ridge, contrast, lfc_null, alt);
 }
 
+// ---- many contrasts of one fit: wald_wide split into the factorisation (once per gene) and the per-contrast tail; same
+// operations in the same order.  wald_wide itself (it also serves the fused LFC epilogue) is left as it is.
+// W.L = chol(W.M + ridge) (W.dM holds the sum)
+template <class Wv, int MP>
+DSQ_HD void wald_wide_factor(const WideWorkT<MP>& W, const double* ridge) {
+    const int P = W.P, ld = W.ld;
+    for (int e = Wv::lane(); e < P * P; e += Wv::W) {
+        const int i = e / P, j = e % P;
+        W.dM[i * ld + j] = W.M[i * ld + j] + ridge[i * P + j];
+    }
+    Wv::sync();
+    wide_chol<Wv>(W, W.dM, W.L, 0.0);
+}
+
+// one contrast given W.M, W.L of wald_wide_factor and beta = W.v(0); uses v(3), v(4)
+template <class Wv, int MP>
+DSQ_HD WaldOut wald_wide_tail(const WideWorkT<MP>& W, const double* contrast, double lfc_null, int alt) {
+    const int P = W.P, ld = W.ld;
+    Wv::sync();  // the previous contrast's readers of v(3), v(4) are done
+    for (int j = Wv::lane(); j < P; j += Wv::W) W.v(3)[j] = contrast[j];
+    Wv::sync();
+    wide_chol_solve<Wv>(W, W.L, W.v(3));
+    for (int i = Wv::lane(); i < P; i += Wv::W) {
+        double r = 0.0;
+        for (int j = 0; j < P; ++j) r += W.M[i * ld + j] * W.v(3)[j];
+        W.v(4)[i] = r;
+    }
+    Wv::sync();
+    double q = 0.0;
+    for (int j = 0; j < P; ++j) q += W.v(3)[j] * W.v(4)[j];
+    WaldOut o;
+    o.se = sqrt(q);
+    const double* beta = W.v(0);
+    double stat = 0.0, pval;
+    if (alt == ALT_NONE) {
+        double t = 0.0;
+        for (int j = 0; j < P; ++j) t += contrast[j] * (beta[j] - lfc_null);
+        stat = t / o.se;
+        pval = 2.0 * norm_sf(fabs(stat));
+    } else if (alt == ALT_GREATER) {
+        for (int j = 0; j < P; ++j) stat += contrast[j] * np_fmax((beta[j] - lfc_null) / o.se, 0.0);
+        pval = norm_sf(stat);
+    } else if (alt == ALT_LESS) {
+        for (int j = 0; j < P; ++j) stat += contrast[j] * np_fmin((beta[j] - lfc_null) / o.se, 0.0);
+        pval = norm_sf(fabs(stat));
+    } else if (alt == ALT_GREATER_ABS) {
+        for (int j = 0; j < P; ++j)
+            stat += contrast[j] * (dsign(beta[j]) * np_fmax((fabs(beta[j]) - lfc_null) / o.se, 0.0));
+        pval = 2.0 * norm_sf(fabs(stat));
+    } else {
+        const double an = fabs(lfc_null);
+        double sa = 0.0, sb = 0.0;
+        for (int j = 0; j < P; ++j) {
+            sa += contrast[j] * np_fmax((beta[j] + an) / o.se, 0.0);
+            sb += contrast[j] * np_fmin((beta[j] - an) / o.se, 0.0);
+        }
+        const double pa = norm_sf(sa), pb = norm_sf(fabs(sb));
+        stat = (fabs(sb) < fabs(sa)) ? sb : sa;
+        pval = (pb > pa) ? pb : pa;
+    }
+    o.stat = stat;
+    o.p = pval;
+    return o;
+}
+
+// K contrasts ([K][P]) of one gene: the Gram matrix (the loop of wald_gene_wide) and the factorisation once, the tail
+// per contrast, the wavefront working on one contrast at a time.  beta must be in W.v(0); the lane for which `writer`
+// holds stores the gene's K results.
+template <class Wv, int MP>
+DSQ_HD void wald_gene_multi_wide(const double* mu, const double* sf, const double* Xt, int ldx, int N, double disp,
+                                 const WideWorkT<MP>& W, const double* ridge, const double* contrasts, int K,
+                                 double lfc_null, int alt, bool writer, double* pvals, double* stats, double* se) {
+    const int P = W.P;
+    WideGram<Wv, false, MP> gram;
+    gram.begin(W);
+    wide_zero_pad_rows<Wv>(W);
+    Wv::sync();
+    const int n_end = ((N + 63) / 64) * 64;
+    for (int n0 = 0; n0 < n_end; n0 += 64) {
+        wide_stage_x<Wv>(W, Xt, ldx, N, n0);
+        Wv::sync();
+        for (int l = Wv::lane(); l < 64; l += Wv::W) {
+            const int n = n0 + l;
+            double w = 0.0;
+            if (n < N) {
+                double m;
+                if (mu != nullptr) m = mu[n];
+                else {
+                    double eta = 0.0;
+                    for (int j = 0; j < P; ++j) eta += W.xs[j * kWideXsLd + l] * W.v(0)[j];
+                    m = sf[n] * exp(eta);
+                }
+                w = m / (1.0 + m * disp);
+            }
+            W.w[l] = w;
+        }
+        Wv::sync();
+        gram.add_chunk(W);
+        Wv::sync();
+    }
+    gram.finish(W);
+    wald_wide_factor<Wv>(W, ridge);
+    for (int k = 0; k < K; ++k) {
+        const WaldOut o = wald_wide_tail<Wv>(W, contrasts + (size_t)k * P, lfc_null, alt);
+        if (writer) {
+            pvals[k] = o.p;
+            stats[k] = o.stat;
+            se[k] = o.se;
+        }
+    }
+}
+
 }  // namespace dsq

@@ -1397,6 +1397,40 @@ class DeseqPipeline:
             se[z], st[z], pv[z] = 0.0, 0.0, 1.0
         return pv, st, se
 
+    def wald_multi(self, res: DeseqResult, contrasts, lfc_null=0.0, alt_hypothesis=None, lfc=None, ridge=None):
+        """Wald tests of K contrasts of the same fit (``contrasts``: K x P) in one launch: per gene X^T W X is accumulated
+        and factored once (k_wald_multi / k_wald_multi_wide), only the per-contrast tail repeats.  One upload of size
+        factors, coefficients and dispersions, one download.  Arguments as wald(); returns (pvalue, stat, lfcSE), each
+        K x G, row k what wald(res, contrasts[k], ...) returns.  (Single process: DistributedDeseq has no counterpart.)"""
+        if alt_hypothesis not in ALT:
+            raise KeyError(alt_hypothesis)
+        if lfc_null < 0 and alt_hypothesis in {"greaterAbs", "lessAbs"}:
+            raise ValueError(f"The alternative hypothesis being {alt_hypothesis}, please provide a "
+                             f"positive lfc_null value (got {lfc_null}).")
+        G, N, P, D = self.G, self.N, self.P, self.design
+        contrasts = np.ascontiguousarray(contrasts, dtype=np.float64)
+        if contrasts.ndim != 2:
+            raise ValueError("wald_multi() takes a K x P matrix of contrasts; use wald() for a single contrast vector.")
+        K = contrasts.shape[0]
+        if K < 1 or contrasts.shape[1] != P:
+            raise ValueError(f"contrasts must be K x {P} with K >= 1 (got {contrasts.shape[0]} x {contrasts.shape[1]}).")
+        ridge = np.ascontiguousarray(np.diag(np.repeat(1e-6, P)) if ridge is None else ridge, dtype=np.float64)
+        ctx = self.ctx
+        d_sf = DeviceArray.from_host(ctx, np.ascontiguousarray(res.size_factors, dtype=np.float64))
+        d_beta = DeviceArray.from_host(ctx, np.ascontiguousarray(res.LFC if lfc is None else lfc, dtype=np.float64))
+        d_disp = DeviceArray.from_host(ctx, np.ascontiguousarray(res.dispersions, dtype=np.float64))
+        d_con = DeviceArray.from_host(ctx, contrasts)
+        d_out = DeviceArray(ctx, (3 * G * K,), np.float64)
+        ctx.call("dsq_dev_wald_multi", None, self.ldn, _vp(d_sf.ptr), _vp(self.d_Xt.ptr), D.ldx, N, G, P, _vp(d_disp.ptr),
+                 _vp(d_beta.ptr), _vp(ridge.ctypes.data), _vp(d_con.ptr), K, c_double(np.log(2) * lfc_null),
+                 ALT[alt_hypothesis], _vp(d_out.ptr), _vp(d_out.ptr + 8 * G * K), _vp(d_out.ptr + 16 * G * K))
+        o = d_out.to_host().reshape(3, G, K)
+        pv, st, se = (np.ascontiguousarray(o[i].T) for i in range(3))
+        z = np.asarray(res.new_all_zeroes, dtype=bool)
+        if z.any():  # ds.py:357-360
+            se[:, z], st[:, z], pv[:, z] = 0.0, 0.0, 1.0
+        return pv, st, se
+
     # ------------------------------------------------------------------ likelihood-ratio test
     def lrt(self, res: DeseqResult, reduced_design):
         """Likelihood-ratio test of a nested reduced design (DESeq2's nbinomLRT) on the dispersions / LFCs of ``res``,
