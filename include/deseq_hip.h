@@ -492,6 +492,16 @@ int dsq_dev_lrt(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, c
 /* d_out[i] = survival function of the chi-square distribution with df degrees of freedom (an integer, 1 ... 127) at
  * d_x[i] (scipy.stats.chi2.sf): 1 for x <= 0. */
 int dsq_dev_chisq_sf(dsq_ctx* ctx, const double* d_x, int n, int df, double* d_out);
+/* Regularized-log transformation (DESeq2's rlog(); csrc/dsq_rlog.h): per gene the ridge-penalised NB GLM with an
+ * intercept and one coefficient per sample (penalty 1 / beta_prior_var on the log2 scale, 1e-6 on the intercept), fitted by
+ * IRLS from the intercept ln d_base_mean[g] at the TREND dispersion d_disp_fit[g] (deviance criterion 1e-4, at most 100
+ * iterations, mu >= 0.5, |coefficient| <= 30 natural-log units).  d_y: gene-major int32 rows of pitch ldn; d_out [G][N]:
+ * log2 (intercept + sample coefficient); d_intercept [G] log2; d_conv [G] uint8; d_niter [G] int32 (100: not converged).
+ * A gene whose base mean is not positive gets a row of zeros, intercept 0, 0 iterations, not converged.  Any N >= 1.
+ * DSQ_ERR_ARG: N < 1, G < 0, beta_prior_var not finite or not positive, a null output; G == 0 does nothing. */
+int dsq_dev_rlog(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, int N, int G, const double* d_disp_fit,
+                 const double* d_base_mean, double beta_prior_var, double* d_out, double* d_intercept, uint8_t* d_conv,
+                 int32_t* d_niter);
 /* row gathers for the refit sub-problem: dst[k][:] = src[idx[k]][:] */
 /* O(G) glue that keeps the dispersion vectors device-resident between the stages:
  * fitted trend a0 + a1/normed_mean (dds.py:826-833; a1 == 0: mean trend), final dispersions with the

@@ -713,6 +713,44 @@ class DeseqDataSet:
             return self._pipe.vst_transform(self.obs["size_factors"].to_numpy(), **self._vst_params)
         return self._pipe.vst_transform_new(np.asarray(counts), self.logmeans, self.filtered_genes, **self._vst_params)
 
+    def rlog(self, use_design: bool = False, fit_type=None, beta_prior_var=None):
+        """Regularized-log transformation into ``layers["rlog_counts"]`` (DESeq2's ``rlog()``, which the reference does not
+        have): log2 of the fitted means of a per-gene ridge-penalised GLM with one coefficient per sample,
+        which shrinks the sample differences of genes with low counts.  Like ``vst()``: size factors, genewise dispersions
+        and trend are fitted first - with an intercept-only design unless ``use_design`` (DESeq2's ``blind = TRUE``) and
+        with ``fit_type`` (default: the data set's) - and the transformation uses the TREND dispersions.
+        ``beta_prior_var``: the prior variance of the sample coefficients on the log2 scale; None: estimated from the data.
+        Fills ``var["rlog_intercept"]``, ``var["rlog_converged"]``, ``var["rlog_fitted_dispersions"]`` and
+        ``uns["rlog_beta_prior_var"]``; genes without counts get 0 in every sample and NaN there."""
+        ft = fit_type if fit_type is not None else self.fit_type
+        if ft not in ("parametric", "mean"):
+            raise NotImplementedError(f"Found fit_type '{ft}'. Expected 'parametric' or 'mean'.")
+        if beta_prior_var is not None and not (np.isfinite(beta_prior_var) and beta_prior_var > 0):
+            raise ValueError(f"beta_prior_var must be a finite positive number (got {beta_prior_var}).")
+        p0 = self._pipe
+        X = self.obsm["design_matrix"].to_numpy() if use_design else np.ones((self.n_obs, 1))
+        pipe = p0 if use_design else DeseqPipeline(self.X, X, ctx=p0.ctx, min_mu=p0.min_mu, min_disp=p0.min_disp,
+                                                    max_disp=p0.max_disp, beta_tol=p0.beta_tol, fit_type=ft,
+                                                    size_factors_fit_type=p0.size_factors_fit_type,
+                                                    control_genes=self._control_genes)
+        old_ft, pipe.fit_type = pipe.fit_type, ft  # (as vst_fit: the size factors are refitted, the trend may fall back)
+        try:
+            r = pipe.deseq2(stop_after_trend=True)
+            out, b0, conv, _, bpv = pipe.rlog(r, beta_prior_var)
+        finally:
+            pipe.fit_type = old_ft
+            if pipe is not p0:
+                pipe.close()
+        if pipe is p0:
+            self._step = None  # (the device layers of an earlier fit were recycled by this run: rebuilt when read)
+        self._set_size_factors(r.size_factors)
+        self.layers.offer("normed_counts")
+        self.layers["rlog_counts"] = out
+        self.var["rlog_intercept"], self.var["rlog_converged"] = b0, conv
+        self.var["rlog_fitted_dispersions"] = np.array(r.fitted_dispersions)
+        self.uns["rlog_beta_prior_var"] = bpv
+        return self.layers["rlog_counts"]
+
     @property
     def non_zero_genes(self):
         return self.var_names[np.asarray(self.var["non_zero"], dtype=bool)]

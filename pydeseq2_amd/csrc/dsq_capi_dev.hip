@@ -628,6 +628,23 @@ int dsq_dev_chisq_sf(dsq_ctx* ctx, const double* d_x, int n, int df, double* d_o
     return DSQ_OK;
 }
 
+int dsq_dev_rlog(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, int N, int G, const double* d_disp_fit,
+                 const double* d_base_mean, double beta_prior_var, double* d_out, double* d_intercept, uint8_t* d_conv,
+                 int32_t* d_niter) {
+    DSQ_CHECK_ARG(N >= 1, "N: at least one sample");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(std::isfinite(beta_prior_var) && beta_prior_var > 0.0, "beta_prior_var: a finite positive number");
+    DSQ_CHECK_ARG(d_out != nullptr && d_intercept != nullptr && d_conv != nullptr && d_niter != nullptr,
+                  "an output pointer is null");
+    if (G == 0) return DSQ_OK;
+    DSQ_CHECK_ARG(d_y != nullptr && d_sf != nullptr && d_disp_fit != nullptr && d_base_mean != nullptr,
+                  "an input pointer is null");
+    DSQ_CHECK_ARG(ldn >= N, "ldn is smaller than N");
+    DSQ_HIP(dsq::launch_rlog(ctx->stream, d_y, ldn, d_sf, N, G, d_disp_fit, d_base_mean, beta_prior_var, d_out, d_intercept,
+                             d_conv, d_niter));
+    return DSQ_OK;
+}
+
 int dsq_dev_gather_rows_f64(dsq_ctx* ctx, const double* d_src, int ld, const int32_t* d_idx, int n_idx,
                             int ncols, double* d_dst) {
     DSQ_HIP(dsq::launch_gather_rows_f64(ctx->stream, d_src, ld, d_idx, n_idx, ncols, d_dst));

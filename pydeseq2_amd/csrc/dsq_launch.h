@@ -326,6 +326,11 @@ hipError_t launch_lrt(hipStream_t st, const int32_t* y, int ldn, const double* s
                       const double* Xr, int ldr, int Pr, int N, int G, const double* disp, const double* beta_f,
                       const double* beta_r, double* stat, double* pval);
 hipError_t launch_chisq_sf(hipStream_t st, const double* x, int n, int df, double* out);
+// ---- dsq_k_rlog.hip: regularized-log transformation (dsq_rlog.h): out [G][N] log2, one gene per wavefront; samples in
+// registers up to N = 512, in the output row beyond
+hipError_t launch_rlog(hipStream_t st, const int32_t* y, int ldn, const double* sf, int N, int G, const double* disp,
+                       const double* base_mean, double beta_prior_var, double* out, double* intercept, uint8_t* conv,
+                       int32_t* niter);
 hipError_t launch_cooks(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* mu,
                         const double* hat, const int32_t* cell_offsets, const int32_t* cell_index,
                         int n_cells, int whole, int max_cell, const uint8_t* flags, int N, int G,

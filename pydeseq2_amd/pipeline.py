@@ -1000,8 +1000,9 @@ class DeseqPipeline:
             r.disp_function_type = "mean"
             r.mean_disp = self._mean_trend(Gn)
             st.a0, st.a1 = float(r.mean_disp), 0.0
-        if only_trend:  # vst_fit (dds.py:384-438): size factors, genewise dispersions, trend
-            self.publish(st, ("nm", "mom", "gw", "gconv"))
+        if only_trend:  # vst_fit (dds.py:384-438): size factors, genewise dispersions, trend (+ its values: rlog() fits at them)
+            self.ctx.call("dsq_dev_trend_eval", _vp(S["nm"].ptr), Gn, c_double(st.a0), c_double(st.a1), _vp(S["fit"].ptr))
+            self.publish(st, ("nm", "mom", "gw", "gconv", "fit"))
             return
         if fused_sq is None or coeffs is None:
             self.ctx.call("dsq_dev_trend_eval", _vp(S["nm"].ptr), Gn, c_double(st.a0), c_double(st.a1), _vp(S["fit"].ptr))
@@ -1514,6 +1515,71 @@ class DeseqPipeline:
         if z.any():  # ds.py:357-360, dds.py:1380-1383
             stt[z], pv[z], beta_r[z] = 0.0, 1.0, 0.0
         return pv, stt, beta_r, conv_r
+
+    # ------------------------------------------------------------------ regularized-log transformation
+    def rlog(self, res: DeseqResult, beta_prior_var=None):
+        """Regularized-log transformation (DESeq2's rlog(); csrc/dsq_rlog.h) of the resident counts, post hoc
+        like wald() / lrt(): per gene a ridge-penalised NB GLM with an intercept and one coefficient per sample, fitted at
+        the TREND dispersions ``res.fitted_dispersions`` from the intercept log ``res.normed_means`` with the size factors
+        of ``res`` - a result of ``deseq2()`` or of ``deseq2(stop_after_trend=True)``.  ``beta_prior_var`` (log2 scale):
+        the prior variance of the sample coefficients; None: estimated on the host from all genes with counts
+        (pydeseq2_amd/rlog.py).  One launch.
+        Returns (rlog N x G in log2, intercept, converged, n_iter, beta_prior_var); genes without counts: rlog 0 in every
+        sample, intercept / converged / n_iter NaN."""
+        from .rlog import beta_prior_var as estimate_prior_var
+
+        G, N, ctx = self.G, self.N, self.ctx
+        if res.fitted_dispersions is None:
+            raise ValueError("rlog(): the result carries no fitted_dispersions (run deseq2(), or "
+                             "deseq2(stop_after_trend=True), first).")
+        nz = np.asarray(res.non_zero, dtype=bool)
+        nzi = np.nonzero(nz)[0]
+        Gn = len(nzi)
+        fit = np.asarray(res.fitted_dispersions, dtype=np.float64)[nzi]
+        if not (np.isfinite(fit) & (fit > 0)).all():
+            raise ValueError("rlog(): fitted_dispersions is not a finite positive number on every gene with counts.")
+        if beta_prior_var is not None and not (np.isfinite(beta_prior_var) and beta_prior_var > 0):
+            raise ValueError(f"rlog(): beta_prior_var must be a finite positive number (got {beta_prior_var}).")
+        sf = np.ascontiguousarray(res.size_factors, dtype=np.float64)
+        out = np.zeros((N, G))
+        b0, conv, nit = np.full(G, np.nan), np.full(G, np.nan), np.full(G, np.nan)
+        if Gn == 0:
+            return out, b0, conv, nit, (float(beta_prior_var) if beta_prior_var is not None else np.nan)
+        if beta_prior_var is None:
+            beta_prior_var = estimate_prior_var(self.d_raw.to_host()[:, nzi], sf, fit)
+            if not (np.isfinite(beta_prior_var) and beta_prior_var > 0):
+                raise ValueError(f"rlog(): the estimated beta_prior_var is {beta_prior_var} (no count differs from its "
+                                 "gene's mean, as with a single sample): give beta_prior_var.")
+        beta_prior_var = float(beta_prior_var)
+        held = []
+
+        def dev(a):
+            held.append(DeviceArray.from_host(ctx, np.ascontiguousarray(a)))
+            return held[-1]
+
+        try:
+            d_sf, d_fit = dev(sf), dev(fit)
+            d_bm = dev(np.asarray(res.normed_means, dtype=np.float64)[nzi])
+            if Gn == G:
+                d_y = self.d_y
+            else:
+                d_idx = dev(nzi.astype(np.int32))
+                d_y = DeviceArray(ctx, (Gn, N), np.int32, ld=self.ldn)
+                held.append(d_y)
+                ctx.call("dsq_dev_gather_rows_i32", _vp(self.d_y.ptr), self.ldn, _vp(d_idx.ptr), Gn, N, _vp(d_y.ptr))
+            d_out = DeviceArray(ctx, (Gn, N), np.float64)
+            d_b0, d_cv, d_it = DeviceArray(ctx, (Gn,), np.float64), DeviceArray(ctx, (Gn,), np.uint8), \
+                DeviceArray(ctx, (Gn,), np.int32)
+            held.extend([d_out, d_b0, d_cv, d_it])
+            self._k("rlog", Gn, "dsq_dev_rlog", _vp(d_y.ptr), self.ldn, _vp(d_sf.ptr), N, Gn, _vp(d_fit.ptr), _vp(d_bm.ptr),
+                    c_double(beta_prior_var), _vp(d_out.ptr), _vp(d_b0.ptr), _vp(d_cv.ptr), _vp(d_it.ptr))
+            out[:, nzi] = d_out.to_host().T
+            b0[nzi], conv[nzi], nit[nzi] = d_b0.to_host(), d_cv.to_host(), d_it.to_host()
+        finally:
+            ctx.sync()
+            for a in held:
+                a.free()
+        return out, b0, conv, nit, beta_prior_var
 
     def close(self):
         """Release the pooled device buffers."""
