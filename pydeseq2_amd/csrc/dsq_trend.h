@@ -45,6 +45,12 @@ struct TrendPartial {
     int cf = 0, c0 = 0, c1 = 0;
 };
 
+// numpy.clip (dds.py:792-794): a NaN dispersion stays NaN, so that nanmean skips the gene's terms; dmin(dmax()) alone
+// would turn it into min_disp.  A number is clipped as dmin(dmax()) clips it.
+DSQ_HD double trend_clip(double d, double min_disp, double max_disp) {
+    return d != d ? d : dmin(dmax(d, min_disp), max_disp);
+}
+
 DSQ_HD int trend_init_keep(const TrendData& D, int first, int stride) {
     int kept = 0;
     for (int i = first; i < D.n; i += stride) {
@@ -62,7 +68,7 @@ DSQ_HD void trend_eval_partial(const TrendData& D, int first, int stride, double
     for (int i = first; i < D.n; i += stride) {
         if (!D.keep[i]) continue;
         const double cov = D.raw ? D.means[i] : frcp(D.means[i]);
-        const double t = D.raw ? D.disp[i] : dmin(dmax(D.disp[i], D.min_disp), D.max_disp);
+        const double t = D.raw ? D.disp[i] : trend_clip(D.disp[i], D.min_disp, D.max_disp);
         const double mu = a0 + a1 * cov;
         const double rmu = frcp(mu);
         const double tm = t * rmu;
@@ -79,7 +85,7 @@ DSQ_HD int trend_filter(const TrendData& D, int first, int stride, double a0, do
     int k2 = 0;
     for (int i = first; i < D.n; i += stride) {
         if (!D.keep[i]) continue;
-        const double t = dmin(dmax(D.disp[i], D.min_disp), D.max_disp);
+        const double t = trend_clip(D.disp[i], D.min_disp, D.max_disp);
         const double ratio = t / (a0 + a1 * (1.0 / D.means[i]));
         if (ratio < 1e-4 || ratio >= 15.0) D.keep[i] = 0;  // dds.py:1254-1264
         else k2 += 1;

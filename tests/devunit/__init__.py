@@ -1,7 +1,8 @@
 """ctypes front-end of the TEST-ONLY device build of dsq_math.h / dsq_wave.h (see devunit.hip) and of dsq_wide.h /
 dsq_wider.h / row_chol_solve (see devunit_linalg.hip), of dsq_stats.h / dsq_lds_sort.h (see devunit_stats.hip) and of
 dsq_lbfgsb_wave.h / dsq_lbfgsb.h / dsq_lbfgsb_par.h (see devunit_optim.hip), and of dsq_alpha.h's objective and the row
-kernels of the dispersion fit (see devunit_alpha.hip).
+kernels of the dispersion fit (see devunit_alpha.hip), and of the trend fit's passes and the product's trend unit (see
+devunit_trend.hip).
 
 Every function takes numpy arrays, pads them to whole 256-thread blocks where the caller has not, runs one entry point
 (allocate, copy, launch, synchronise, free) and raises on a non-zero hipError_t."""
@@ -586,3 +587,97 @@ def alpha_wg(y, sf, cell_of, Xc, alpha_hat, min_disp, max_disp, min_mu, coef, ev
     wg_grid_count: what k_alpha_wg wrote."""
     return _rows_launch("du_alpha_wg", "rows", y, sf, cell_of, Xc, alpha_hat, min_disp, max_disp, min_mu, coef, None,
                         genes, prior_var, prior_reg, const_mode, eval_cap, nll_const)
+
+
+# ------------------------------------------------------------------------------- dsq_trend_grid.h, dsq_k_trend.hip
+FIT_FIELDS = ("a0", "a1", "ok", "n_outer", "n_kept")
+# the record of one (workgroup, point) of k_probe (devunit_trend.hip)
+PROBE_TOT_LOAD, PROBE_KEPT0, PROBE_E0, PROBE_TOT_E0 = slice(0, 6), 6, slice(7, 10), slice(10, 16)
+PROBE_KEPT1, PROBE_TOT_FILTER, PROBE_E1, PROBE_TOT_E1 = 16, slice(17, 23), slice(23, 26), slice(26, 32)
+
+
+def trend_grid_blocks():
+    return int(lib().du_trend_grid_blocks())
+
+
+def trend_capacity(blocks):
+    """genes the register path of `blocks` workgroups holds"""
+    return blocks * int(lib().du_trend_threads()) * int(lib().du_trend_reg_genes())
+
+
+def trend_fit_seq(cases, min_disp, max_disp, force_grid=0):
+    """dsq::launch_trend_fit for every (disp, means) of `cases`, back to back on one TrendGridMem, one keep mask and one
+    stream.  force_grid: -1 one workgroup, 0 the launcher's crossover, 1 the grid.  Returns out5 [len(cases)][5]
+    (FIT_FIELDS), NaN where a launch wrote nothing."""
+    d = np.ascontiguousarray(np.concatenate([np.asarray(c[0], np.float64).ravel() for c in cases]))
+    m = np.ascontiguousarray(np.concatenate([np.asarray(c[1], np.float64).ravel() for c in cases]))
+    off = np.zeros(len(cases) + 1, np.int32)
+    off[1:] = np.cumsum([np.asarray(c[0]).size for c in cases])
+    if d.size != m.size or any(np.asarray(c[0]).size != np.asarray(c[1]).size for c in cases):
+        raise ValueError("disp and means of a case have one length")
+    out = np.full((len(cases), 5), np.nan)
+    fn = lib().du_trend_fit_seq
+    fn.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int, C.c_double, C.c_double,
+                   C.c_int, C.POINTER(C.c_double)]
+    fn.restype = C.c_int
+    _check(fn(_p(d, C.c_double), _p(m, C.c_double), _p(off, C.c_int), len(cases), float(min_disp), float(max_disp),
+              int(force_grid), _p(out, C.c_double)), f"du_trend_fit_seq(n={np.diff(off).tolist()}, grid={force_grid})")
+    return out
+
+
+def trend_fit(disp, means, min_disp, max_disp, force_grid=0, repeats=1):
+    """`repeats` launches of one case (trend_fit_seq): out5 [repeats][5]"""
+    return trend_fit_seq([(disp, means)] * repeats, min_disp, max_disp, force_grid)
+
+
+def trend_glm(targets, cov, repeats=1):
+    """dsq::launch_trend_glm, the raw one-fit mode: out5 [repeats][5]"""
+    t, c = _d(targets).ravel(), _d(cov).ravel()
+    if t.size != c.size:
+        raise ValueError("targets and cov have one length")
+    out = np.full((repeats, 5), np.nan)
+    fn = lib().du_trend_glm
+    fn.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double)]
+    fn.restype = C.c_int
+    _check(fn(_p(t, C.c_double), _p(c, C.c_double), t.size, int(repeats), _p(out, C.c_double)), f"du_trend_glm(n={t.size})")
+    return out
+
+
+def trend_probe(blocks, disp, means, min_disp, max_disp, points):
+    """k_probe on 1 or trend_grid_blocks() workgroups: per point init_keep, eval, filter, eval and the six totals of
+    every kind of pass, as EVERY workgroup's leader saw them.  Returns (records [blocks][points][32] - the PROBE_*
+    slices -, the exchange's timeout flag)."""
+    d, m = _d(disp).ravel(), _d(means).ravel()
+    pts = _d(points).reshape(-1, 2)
+    rec = int(lib().du_trend_probe_rec())
+    out = np.full((blocks, pts.shape[0], rec), np.nan)
+    to = C.c_uint(7)
+    fn = lib().du_trend_probe
+    fn.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double,
+                   C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint)]
+    fn.restype = C.c_int
+    _check(fn(int(blocks), _p(d, C.c_double), _p(m, C.c_double), d.size, float(min_disp), float(max_disp),
+              _p(pts, C.c_double), pts.shape[0], _p(out, C.c_double), C.byref(to)), f"du_trend_probe({blocks}, n={d.size})")
+    return out, int(to.value)
+
+
+def trend_loss_grad(cov, targets, a0, a1, keep=None):
+    """dsq::launch_trend_loss_grad (k_trend) and the host's sum of its partials, in dsq_dev_trend_loss_grad's order:
+    (loss, g0, g1, count) - all three sums are divided by the ONE count of NaN-free loss terms."""
+    c, t = _d(cov).ravel(), _d(targets).ravel()
+    k = np.ascontiguousarray(keep, dtype=np.uint8).ravel() if keep is not None else None
+    nb = int(lib().du_trend_partials())
+    part = np.full((nb, 4), np.nan)
+    fn = lib().du_trend_loss_grad
+    fn.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int, C.c_double, C.c_double,
+                   C.POINTER(C.c_double)]
+    fn.restype = C.c_int
+    _check(fn(_p(c, C.c_double), _p(t, C.c_double), _p(k, C.c_uint8), c.size, float(a0), float(a1), _p(part, C.c_double)),
+           f"du_trend_loss_grad(n={c.size})")
+    s = [0.0, 0.0, 0.0, 0.0]
+    for row in part.tolist():
+        for q in range(4):
+            s[q] += row[q]
+    cnt = s[3]
+    with np.errstate(all="ignore"):
+        return np.float64(s[0]) / cnt, -np.float64(s[1]) / cnt, -np.float64(s[2]) / cnt, cnt

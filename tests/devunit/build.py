@@ -13,12 +13,15 @@ SRC_LINALG = os.path.join(HERE, "devunit_linalg.hip")  # dsq_wide.h, dsq_wider.h
 SRC_STATS = os.path.join(HERE, "devunit_stats.hip")  # dsq_stats.h, dsq_lds_sort.h
 SRC_OPTIM = os.path.join(HERE, "devunit_optim.hip")  # dsq_lbfgsb_wave.h, dsq_lbfgsb.h, dsq_lbfgsb_par.h
 SRC_ALPHA = os.path.join(HERE, "devunit_alpha.hip")  # dsq_alpha.h; launches the two row-kernel units below
+SRC_TREND = os.path.join(HERE, "devunit_trend.hip")  # dsq_trend_grid.h; launches the trend unit below
 INC = os.path.join(ROOT, "pydeseq2_amd", "csrc")
 # the product's row kernels of the dispersion fit, unchanged and with the product's flags: devunit_alpha.hip calls their
 # launch_* entry points (dsq_launch.h)
 SRC_ROWS = os.path.join(INC, "dsq_k_alpha_rows.hip")
 SRC_ROWSC = os.path.join(INC, "dsq_k_alpha_rowsc.hip")
-SRCS = [SRC, SRC_LINALG, SRC_STATS, SRC_OPTIM, SRC_ALPHA, SRC_ROWS, SRC_ROWSC]
+# the product's trend kernels and their launchers, likewise: devunit_trend.hip calls launch_trend_fit / _glm / _loss_grad
+SRC_KTREND = os.path.join(INC, "dsq_k_trend.hip")
+SRCS = [SRC, SRC_LINALG, SRC_STATS, SRC_OPTIM, SRC_ALPHA, SRC_TREND, SRC_ROWS, SRC_ROWSC, SRC_KTREND]
 HOST_H = os.path.join(HERE, "devunit_host.h")
 OUT = os.path.join(HERE, "_devunit.so")
 MAKEFILE = os.path.join(INC, "Makefile")

@@ -354,14 +354,27 @@ def bfgs(fg, x0):
     return x, bool(ok.value), nfev.value, nit.value, st.value
 
 
-def trend_fit(disp, means, min_disp, max_disp):
+def trend_fit(disp, means, min_disp, max_disp, with_kept=False):
+    """(coefficients, ok, gamma-GLM fits) and, with_kept, the number of genes in the last fit"""
     d = np.ascontiguousarray(disp, dtype=np.float64)
     m = np.ascontiguousarray(means, dtype=np.float64)
     c = np.empty(2)
-    ok, no = C.c_int(), C.c_int()
+    ok, no, nk = C.c_int(), C.c_int(), C.c_int()
     lib().hs_trend_fit(_p(d, C.c_double), _p(m, C.c_double), C.c_int(len(d)), C.c_double(min_disp),
-                       C.c_double(max_disp), _p(c, C.c_double), C.byref(ok), C.byref(no))
-    return c, bool(ok.value), no.value
+                       C.c_double(max_disp), _p(c, C.c_double), C.byref(ok), C.byref(no), C.byref(nk))
+    return (c, bool(ok.value), no.value, nk.value) if with_kept else (c, bool(ok.value), no.value)
+
+
+def trend_eval(disp, means, min_disp, max_disp, a0, a1):
+    """WaveTrendOps<HostWave>: initial mask, eval, filter, eval at (a0, a1) ->
+    (kept0, {f, g0, g1} before the filter, kept1, {f, g0, g1} after it)"""
+    d = np.ascontiguousarray(disp, dtype=np.float64)
+    m = np.ascontiguousarray(means, dtype=np.float64)
+    kept = np.zeros(2, np.int32)
+    fg = np.full(6, -7.0)
+    lib().hs_trend_eval(_p(d, C.c_double), _p(m, C.c_double), C.c_int(len(d)), C.c_double(min_disp),
+                        C.c_double(max_disp), C.c_double(a0), C.c_double(a1), _p(kept, C.c_int), _p(fg, C.c_double))
+    return (int(kept[0]), dict(f=fg[0], g0=fg[1], g1=fg[2]), int(kept[1]), dict(f=fg[3], g0=fg[4], g1=fg[5]))
 
 
 def flog(x):

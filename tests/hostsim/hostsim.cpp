@@ -565,12 +565,27 @@ int hs_lbfgsb_nd48(fgn_cb cb, int n, double* x, const double* l, const double* u
 }
 
 int hs_trend_fit(const double* disp, const double* means, int n, double min_disp, double max_disp,
-                 double* coeffs, int* ok, int* n_outer) {
+                 double* coeffs, int* ok, int* n_outer, int* n_kept) {
     std::vector<uint8_t> keep(n + 1);
     static TrendWork W;
     std::memset(&W, g_hs_fill, sizeof(W));
     TrendOut o = trend_fit<HostWave>(disp, means, n, min_disp, max_disp, keep.data(), W);
     coeffs[0] = o.a0; coeffs[1] = o.a1; *ok = o.ok; *n_outer = o.n_outer;
+    if (n_kept) *n_kept = o.n_kept;
+    return 0;
+}
+
+// the passes of the fit one by one at (a0, a1): initial mask, eval, filter, eval.
+// kept: the two kept counts, fg [2][3]: {f, g0, g1} before and after the filter
+int hs_trend_eval(const double* disp, const double* means, int n, double min_disp, double max_disp, double a0,
+                  double a1, int* kept, double* fg) {
+    std::vector<uint8_t> keep(n + 1);
+    WaveTrendOps<HostWave> ops;
+    ops.D = TrendData{disp, means, keep.data(), n, min_disp, max_disp};
+    kept[0] = ops.init_keep();
+    ops.eval(a0, a1, fg[0], fg + 1);
+    kept[1] = ops.filter(a0, a1);
+    ops.eval(a0, a1, fg[3], fg + 4);
     return 0;
 }
 

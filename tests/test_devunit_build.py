@@ -40,23 +40,43 @@ def test_flags_are_the_makefiles():
     assert dub.asm_cmd("x.s")[1:1 + len(flags)] == flags
 
 
-def test_sources_are_the_five_units_and_the_two_row_kernel_units_of_the_product():
-    """devunit_alpha.hip launches the product's row kernels: their two units are compiled into the library from csrc/
-    itself, with the same flags, and stay out of the assembly listing (which shows the branches the HEADERS took)."""
+def test_sources_are_the_test_units_and_the_product_units_they_launch():
+    """devunit_alpha.hip launches the product's row kernels and devunit_trend.hip the product's trend kernels: those
+    three units are compiled into the library from csrc/ itself, with the same flags, and stay out of the assembly
+    listing (which shows the branches the HEADERS took)."""
     rel = [os.path.relpath(p, dub.ROOT) for p in dub.SRCS]
     assert rel == ["tests/devunit/devunit.hip", "tests/devunit/devunit_linalg.hip", "tests/devunit/devunit_stats.hip",
-                   "tests/devunit/devunit_optim.hip", "tests/devunit/devunit_alpha.hip",
-                   "pydeseq2_amd/csrc/dsq_k_alpha_rows.hip", "pydeseq2_amd/csrc/dsq_k_alpha_rowsc.hip"]
+                   "tests/devunit/devunit_optim.hip", "tests/devunit/devunit_alpha.hip", "tests/devunit/devunit_trend.hip",
+                   "pydeseq2_amd/csrc/dsq_k_alpha_rows.hip", "pydeseq2_amd/csrc/dsq_k_alpha_rowsc.hip",
+                   "pydeseq2_amd/csrc/dsq_k_trend.hip"]
     assert all(os.path.exists(p) for p in dub.SRCS)
     cmd, asm = dub.compile_cmd(), dub.asm_cmd("x.s")
     assert all(p in cmd for p in dub.SRCS)
-    assert "--include=" + dub.SRC_ALPHA in asm and not any("dsq_k_alpha_rows" in c for c in asm)
+    assert "--include=" + dub.SRC_ALPHA in asm
+    assert not any("dsq_k_alpha_rows" in c or "dsq_k_trend" in c for c in asm)
+    # the product builds the trend unit too (a unit of its own, so that it links here without the rest of dsq_k_stats.hip)
+    assert "dsq_k_trend.hip" in dub.makefile_var("SRCS").split()
 
 
 @needs_hipcc
 def test_builds():
     out = dub.build()
     assert os.path.getsize(out) > 0
+
+
+@needs_hipcc
+@pytest.mark.skipif(shutil.which("nm") is None, reason="nm not installed")
+def test_the_library_has_no_undefined_product_symbol():
+    """Every dsq:: function the test units call is defined by a product unit in the library: a launcher that moved to a
+    unit which is not linked here would only fail when the library is loaded on the GPU machine."""
+    out = dub.build()
+    syms = subprocess.run(["nm", "-C", "-D", "--undefined-only", out], check=True, capture_output=True, text=True).stdout
+    assert "hipLaunchKernel" in syms  # the listing is the library's
+    assert [ln for ln in syms.splitlines() if "dsq::" in ln] == []
+    defined = subprocess.run(["nm", "-C", "-D", "--defined-only", out], check=True, capture_output=True, text=True).stdout
+    for name in ("dsq::launch_trend_fit(", "dsq::launch_trend_glm(", "dsq::launch_trend_loss_grad(",
+                 "dsq::trend_grid_mem_bytes("):
+        assert name in defined, name
 
 
 @needs_hipcc
