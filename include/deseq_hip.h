@@ -38,7 +38,8 @@ extern "C" {
 #define DSQ_MAX_P 128       /* design columns; up to 12 run the register / cell kernels, 13 ... 48 the LDS + MFMA path, 49 ... 128 the
                                device-memory + MFMA path (dsq_wider.h) */
 #define DSQ_SHRINK_MAX_P 48 /* apeGLM shrinkage (dsq_*_lfc_shrink*): up to 12 columns in registers, 13 ... 48 run-time p */
-#define DSQ_BFGS_MAX_P 12   /* optimizer = "BFGS" of the dispersion fit / the IRLS rescue: register kernels only */
+#define DSQ_ASH_MAX_M 48    /* adaptive shrinkage (dsq_dev_ash): mixture components per contrast */
+#define DSQ_BFGS_MAX_P 12  /* optimizer = "BFGS" of the dispersion fit / the IRLS rescue: register kernels only */
 
 typedef struct dsq_ctx dsq_ctx;
 
@@ -502,6 +503,20 @@ int dsq_dev_chisq_sf(dsq_ctx* ctx, const double* d_x, int n, int df, double* d_o
 int dsq_dev_rlog(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, int N, int G, const double* d_disp_fit,
                  const double* d_base_mean, double beta_prior_var, double* d_out, double* d_intercept, uint8_t* d_conv,
                  int32_t* d_niter);
+/* Adaptive shrinkage (Stephens' ashr as DESeq2's lfcShrink(type = "ashr") calls it; csrc/dsq_ash.h) of K
+ * contrasts at once.  Per contrast k: from d_lfc[k][g], d_se[k][g] (rows of pitch ldg; a gene is used if both are finite and
+ * the SE is positive) the mixture proportions of a zero-mean normal mixture with the standard deviations d_sd[k][0 .. m_k)
+ * (row pitch ldm, chosen by the caller: pydeseq2_amd.ash.mixsd_grid) are fitted by sequential quadratic programming on an
+ * active set (at most max_iter Newton steps, stop at min gradient >= -1e-8), one workgroup per contrast; then per gene the
+ * posterior mean, posterior standard deviation and local false sign rate.  Outputs: d_pi [K][ldm] (sums to 1),
+ * d_post_mean / d_post_sd / d_lfsr [K][ldg] (NaN for unused genes), d_niter int32 [K], d_conv uint8 [K], d_kkt [K]
+ * (max_m d_m - 1 at the returned point), d_loglik [K].  Everything on the scale of the inputs.  A contrast without used
+ * genes: NaN in every output, 0 iterations, not converged.
+ * DSQ_ERR_ARG: K < 1, G < 0, ldg < G, an m_k outside 0 ... 48, ldm < max m_k, max_iter < 1, a null pointer.  G == 0, or
+ * m_k == 0 for a contrast, does nothing for that contrast. */
+int dsq_dev_ash(dsq_ctx* ctx, const double* d_lfc, const double* d_se, int G, int ldg, int K, const double* d_sd,
+                const int32_t* d_m, int ldm, int max_iter, double* d_pi, double* d_post_mean, double* d_post_sd,
+                double* d_lfsr, int32_t* d_niter, uint8_t* d_conv, double* d_kkt, double* d_loglik);
 /* row gathers for the refit sub-problem: dst[k][:] = src[idx[k]][:] */
 /* O(G) glue that keeps the dispersion vectors device-resident between the stages:
  * fitted trend a0 + a1/normed_mean (dds.py:826-833; a1 == 0: mean trend), final dispersions with the

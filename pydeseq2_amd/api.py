@@ -1001,6 +1001,7 @@ class DeseqStats:
 
     def run_wald_test(self):
         """Wald test of the CURRENT coefficients (``self.LFC``: shrunk ones after ``lfc_shrink``), ds.py:303-360."""
+        self._drop_ash()  # (an adaptive shrinkage belongs to the test it was made from)
         r = self.dds._res
         pv, st, se = self.dds._pipe.wald(r, self.contrast_vector, self.lfc_null, self.alt_hypothesis,
                                          lfc=self.LFC.to_numpy(), ridge=self._ridge())
@@ -1050,8 +1051,12 @@ class DeseqStats:
         df = pd.DataFrame(index=self.dds.var_names)
         df["baseMean"] = self.base_mean
         df["log2FoldChange"] = self.LFC.to_numpy() @ self.contrast_vector / np.log(2)
+        if getattr(self, "ash_LFC", None) is not None:  # (adaptive shrinkage of the contrast: kept, like apeGLM's column)
+            df["log2FoldChange"] = self.ash_LFC / np.log(2)
         df["lfcSE"] = self.SE / np.log(2)
         df["stat"], df["pvalue"], df["padj"] = self.statistics, self.p_values, self.padj
+        if getattr(self, "_ash_svalue", False):
+            df["svalue"] = self.svalues
         self.results_df = df
         return df
 
@@ -1104,8 +1109,25 @@ class DeseqStats:
         """Pickles with its data set (examples/plot_step_by_step.py:243-246); device buffers are not part of the state."""
         return dict(self.__dict__)
 
-    def lfc_shrink(self, coeff: str, adapt: bool = True) -> pd.DataFrame:
-        """apeGLM shrinkage of one LFC column, p-values unchanged (ds.py:363-447)."""
+    def lfc_shrink(self, coeff: str = None, adapt: bool = True, *, type: str = "apeglm", svalue: bool = False) -> pd.DataFrame:
+        """Shrinkage of the log fold changes, p-values unchanged.
+
+        ``type="apeglm"`` (the default; ds.py:363-447): apeGLM shrinkage of one LFC column ``coeff`` of the design.
+        ``type="ashr"`` (DESeq2's ``lfcShrink(type="ashr")``, which the reference does not have): adaptive
+        shrinkage of THIS object's contrast, whatever it is - a pairwise comparison that is no design column, a numeric
+        vector -, from its LFC and standard error alone; ``coeff`` must be None.  Stores ``ash_LFC`` (natural log),
+        ``SE`` (the posterior standard deviation), ``lfsr``, ``svalues`` and ``ash_fit`` (pi, grid, n_iter, converged, kkt,
+        loglik), updates ``results_df`` if there is one (with an ``svalue`` column if ``svalue``), and warns if the fit of
+        the mixture did not converge.  Works after ``test="LRT"`` as well."""
+        if type not in ("apeglm", "ashr"):
+            raise ValueError(f"lfc_shrink: type must be 'apeglm' or 'ashr' (got {type!r}).")
+        if type == "ashr":
+            if coeff is not None:
+                raise ValueError("lfc_shrink(type='ashr') shrinks the contrast of this DeseqStats: coeff must be None "
+                                 f"(got {coeff!r}).")
+            DeseqStats.shrink_batch([self], svalue=svalue)
+            return self.results_df if hasattr(self, "results_df") else None
+        self._drop_ash()
         if coeff not in self.LFC.columns:
             raise KeyError(f"The coeff argument '{coeff}' should be one the LFC columns. "
                            f"The available LFC coeffs are {self.LFC.columns[1:]}.")
@@ -1117,7 +1139,7 @@ class DeseqStats:
         if not hasattr(self, "SE"):
             self.run_wald_test()
         r = self.dds._res
-        work = type(r)(**{k: getattr(r, k) for k in r.__dataclass_fields__})
+        work = r.__class__(**{k: getattr(r, k) for k in r.__dataclass_fields__})  # (`type` is the keyword argument here)
         work.LFC, work.lfcSE = self.LFC.to_numpy().copy(), self.SE.to_numpy()
         work.size_factors = np.asarray(self.dds.obs["size_factors"], dtype=float)
         work.dispersions = np.asarray(self.dds.var["dispersions"], dtype=float)
@@ -1131,3 +1153,59 @@ class DeseqStats:
             self.results_df["lfcSE"] = self.SE / np.log(2)
             return self.results_df
         return None
+
+    def _drop_ash(self):
+        """Forget an adaptive shrinkage (the Wald test is about to be re-run, or apeGLM to take over): the standard error
+        goes back to the Wald one with the next run_wald_test()."""
+        if getattr(self, "ash_LFC", None) is None:
+            return
+        self.ash_LFC = self.lfsr = self.svalues = self.ash_fit = None
+        self._ash_svalue = False
+        self.shrunk_LFCs = False
+        if hasattr(self, "_wald_SE"):
+            self.SE = self._wald_SE
+            del self._wald_SE
+
+    @staticmethod
+    def shrink_batch(stats, svalue: bool = False) -> list:
+        """``lfc_shrink(type="ashr")`` of a list of ``DeseqStats`` of ONE data set - ``DeseqStats.batch(dds,
+        pairwise_contrasts(dds, factor))``, say - in one device call (``DeseqPipeline.ash``: one upload, the fit of all
+        contrasts in one launch, the posterior in another, one download).  Each member ends in the state its own
+        ``lfc_shrink(type="ashr", svalue=svalue)`` would leave it in.  Returns the list."""
+        stats = list(stats)
+        if not stats:
+            raise ValueError("DeseqStats.shrink_batch() needs at least one DeseqStats.")
+        dds = stats[0].dds
+        if any(o.dds is not dds for o in stats):
+            raise ValueError("DeseqStats.shrink_batch(): the members must belong to one DeseqDataSet.")
+        for o in stats:
+            o._drop_ash()
+            if not hasattr(o, "SE"):
+                o.run_wald_test()
+                if o.test == "LRT":
+                    del o._wald_key  # (summary() still owes the likelihood-ratio statistic)
+        lfc = np.stack([o.LFC.to_numpy() @ o.contrast_vector for o in stats])
+        se = np.stack([o.SE.to_numpy() for o in stats])
+        res = dds._pipe.ash(lfc, se)
+        idx = dds.var_names
+        for k, o in enumerate(stats):
+            o._wald_SE = o.SE
+            o.ash_LFC = pd.Series(res.post_mean[k], index=idx)
+            o.SE = pd.Series(res.post_sd[k], index=idx)
+            o.lfsr, o.svalues = pd.Series(res.lfsr[k], index=idx), pd.Series(res.svalue[k], index=idx)
+            o.ash_fit = dict(pi=res.pi[k], grid=res.grid[k], n_iter=int(res.n_iter[k]), converged=bool(res.converged[k]),
+                             kkt=float(res.kkt[k]), loglik=float(res.loglik[k]))
+            o._ash_svalue = bool(svalue)
+            o.shrunk_LFCs = True
+            if len(res.grid[k]) and not o.ash_fit["converged"]:
+                warnings.warn(f"lfc_shrink(type='ashr'): the fit of the mixture proportions did not converge for the "
+                              f"contrast {o.contrast!r} ({o.ash_fit['n_iter']} iterations, KKT residual "
+                              f"{o.ash_fit['kkt']:.3g}).", UserWarning, stacklevel=2)
+            if hasattr(o, "results_df"):
+                o.results_df["log2FoldChange"] = o.ash_LFC / np.log(2)
+                o.results_df["lfcSE"] = o.SE / np.log(2)
+                if svalue:
+                    o.results_df["svalue"] = o.svalues
+                elif "svalue" in o.results_df:
+                    del o.results_df["svalue"]
+        return stats

@@ -645,6 +645,33 @@ int dsq_dev_rlog(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, 
     return DSQ_OK;
 }
 
+int dsq_dev_ash(dsq_ctx* ctx, const double* d_lfc, const double* d_se, int G, int ldg, int K, const double* d_sd,
+                const int32_t* d_m, int ldm, int max_iter, double* d_pi, double* d_post_mean, double* d_post_sd,
+                double* d_lfsr, int32_t* d_niter, uint8_t* d_conv, double* d_kkt, double* d_loglik) {
+    DSQ_CHECK_ARG(K >= 1, "K: at least one contrast");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(ldg >= G, "ldg is smaller than G");
+    DSQ_CHECK_ARG(max_iter >= 1, "max_iter: at least one iteration");
+    DSQ_CHECK_ARG(d_lfc != nullptr && d_se != nullptr && d_sd != nullptr && d_m != nullptr, "an input pointer is null");
+    DSQ_CHECK_ARG(d_pi != nullptr && d_post_mean != nullptr && d_post_sd != nullptr && d_lfsr != nullptr &&
+                      d_niter != nullptr && d_conv != nullptr && d_kkt != nullptr && d_loglik != nullptr,
+                  "an output pointer is null");
+    std::vector<int32_t> m((size_t)K);  // (the grid sizes decide the launch: K integers back to the host)
+    DSQ_HIP(hipMemcpyAsync(m.data(), d_m, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    DSQ_HIP(hipStreamSynchronize(ctx->stream));
+    int max_m = 0;
+    for (int k = 0; k < K; ++k) {
+        DSQ_CHECK_ARG(m[k] >= 0 && m[k] <= DSQ_ASH_MAX_M, "m: between 0 and 48 mixture components per contrast");
+        max_m = m[k] > max_m ? m[k] : max_m;
+    }
+    DSQ_CHECK_ARG(ldm >= max_m, "ldm is smaller than the largest m");
+    if (G == 0 || max_m == 0) return DSQ_OK;
+    DSQ_HIP(dsq::launch_ash_fit(ctx->stream, d_lfc, d_se, G, ldg, K, d_sd, d_m, ldm, max_m, max_iter, d_pi, d_niter, d_conv,
+                                d_kkt, d_loglik));
+    DSQ_HIP(dsq::launch_ash_post(ctx->stream, d_lfc, d_se, G, ldg, K, d_sd, d_m, ldm, d_pi, d_post_mean, d_post_sd, d_lfsr));
+    return DSQ_OK;
+}
+
 int dsq_dev_gather_rows_f64(dsq_ctx* ctx, const double* d_src, int ld, const int32_t* d_idx, int n_idx,
                             int ncols, double* d_dst) {
     DSQ_HIP(dsq::launch_gather_rows_f64(ctx->stream, d_src, ld, d_idx, n_idx, ncols, d_dst));

@@ -331,6 +331,13 @@ hipError_t launch_chisq_sf(hipStream_t st, const double* x, int n, int df, doubl
 hipError_t launch_rlog(hipStream_t st, const int32_t* y, int ldn, const double* sf, int N, int G, const double* disp,
                        const double* base_mean, double beta_prior_var, double* out, double* intercept, uint8_t* conv,
                        int32_t* niter);
+// ---- dsq_k_ash.hip: adaptive shrinkage (dsq_ash.h): the mixture fit, one workgroup per contrast (m[k] == 0: skipped),
+// and the posterior summaries, one thread per (contrast, gene)
+hipError_t launch_ash_fit(hipStream_t st, const double* lfc, const double* se, int G, int ldg, int K, const double* sd,
+                          const int32_t* m, int ldm, int max_m, int max_iter, double* pi, int32_t* niter, uint8_t* conv,
+                          double* kkt, double* loglik);
+hipError_t launch_ash_post(hipStream_t st, const double* lfc, const double* se, int G, int ldg, int K, const double* sd,
+                           const int32_t* m, int ldm, const double* pi, double* post_mean, double* post_sd, double* lfsr);
 hipError_t launch_cooks(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* mu,
                         const double* hat, const int32_t* cell_offsets, const int32_t* cell_index,
                         int n_cells, int whole, int max_cell, const uint8_t* flags, int N, int G,

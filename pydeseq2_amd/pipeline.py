@@ -1581,6 +1581,16 @@ class DeseqPipeline:
                 a.free()
         return out, b0, conv, nit, beta_prior_var
 
+    # ------------------------------------------------------------------ adaptive shrinkage
+    def ash(self, lfc, se):
+        """Adaptive shrinkage (Stephens' ashr, DESeq2's lfcShrink(type="ashr"); csrc/dsq_ash.h) of K
+        contrasts from their LFCs and standard errors (K x G each, any scale), post hoc like wald_multi(): the grids on the
+        host, then one upload, the fit of all contrasts in one launch and the posterior in another, one download.  Returns
+        a pydeseq2_amd.ash.AshResult.  (Single process: the gene-sharded pipeline has no counterpart.)"""
+        from .ash import ash
+
+        return ash(self, lfc, se)
+
     def close(self):
         """Release the pooled device buffers."""
         if getattr(self, "_side_pending", False) or getattr(self, "_lfc_forked", False):
