@@ -517,6 +517,31 @@ int dsq_dev_rlog(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, 
 int dsq_dev_ash(dsq_ctx* ctx, const double* d_lfc, const double* d_se, int G, int ldg, int K, const double* d_sd,
                 const int32_t* d_m, int ldm, int max_iter, double* d_pi, double* d_post_mean, double* d_post_sd,
                 double* d_lfsr, int32_t* d_niter, uint8_t* d_conv, double* d_kkt, double* d_loglik);
+/* Sample PCA and sample distances of a transformed matrix (DESeq2's plotPCA and dist on vst / rlog values; csrc/dsq_gram.h,
+ * DESIGN.md 6j).  d_x: N samples x G genes of finite doubles in `layout` (dsq_layout): DSQ_SAMPLE_MAJOR [N][ld], ld >= G, or
+ * DSQ_GENE_MAJOR [G][ld], ld >= N; what lies in the row padding is never read.  All index arithmetic in 64 bits.
+ * dsq_dev_row_meanvar: per gene the mean and the two-pass variance sum (x - mean)^2 / (N - 1) (R's rowVars; N == 1: NaN);
+ *   d_mean [G], d_var [G] or null.
+ * dsq_dev_sample_gram: d_S [N][lds] (both triangles, exactly symmetric) = sum over the K listed genes of
+ *   (x_ig - d_mean[g]) (x_jg - d_mean[g]); d_sel: K int32 gene indices in 0 ... G-1, in any order (NOT checked on the device:
+ *   an index outside the range is the caller's error), or null: the genes 0 ... K-1 (K <= G); d_mean [G] indexed by gene, or
+ *   null: no centring.  The genes are packed (centred, gene-major, zero padding) into the workspace, the Gram is summed on
+ *   the fp64 matrix cores per 128 x 128 macro tile of the lower triangle, each entry over its genes in list order; with
+ *   t = ceil(N / 128), tiles = t (t + 1) / 2, chunks = ceil(K / 32) the list is cut into slices = ceil(chunks / cps) slices of
+ *   cps = ceil(chunks / min(ceil(chunks / 4), max(1, 512 / tiles))) chunks (512 / tiles: integer division; a function of N and K alone), whose
+ *   partial tiles are added in ascending order.  No atomics: the same call gives the same bits.
+ *   d_work: dsq_sample_gram_work_doubles(N, K) = K * pad16(N) doubles of packed panel, plus, when slices > 1,
+ *   slices * tiles * 16384 doubles of partial tiles (at most 512 * 16384 of them: 64 MiB; none from N = 2817 on).
+ *   K == 0 or G == 0: S = 0.
+ * dsq_dev_gram_dist: d_D [N][ldd] = sqrt(max(S_ii + S_jj - 2 S_ij, 0)), 0 on the diagonal.
+ * DSQ_ERR_ARG: N < 1, G < 0, K < 0, K > G without a list, an unknown layout, ld below the row length of the layout, lds or
+ * ldd below N, a null pointer where one is needed (d_var, d_sel and d_mean may be null; d_x and d_work when there is no gene
+ * to read).  G == 0 leaves d_mean / d_var untouched. */
+int dsq_dev_row_meanvar(dsq_ctx* ctx, const double* d_x, int layout, int N, int G, int ld, double* d_mean, double* d_var);
+size_t dsq_sample_gram_work_doubles(int N, int K);
+int dsq_dev_sample_gram(dsq_ctx* ctx, const double* d_x, int layout, int N, int G, int ld, const int32_t* d_sel, int K,
+                        const double* d_mean, double* d_work, double* d_S, int lds);
+int dsq_dev_gram_dist(dsq_ctx* ctx, const double* d_S, int N, int lds, double* d_D, int ldd);
 /* row gathers for the refit sub-problem: dst[k][:] = src[idx[k]][:] */
 /* O(G) glue that keeps the dispersion vectors device-resident between the stages:
  * fitted trend a0 + a1/normed_mean (dds.py:826-833; a1 == 0: mean trend), final dispersions with the

@@ -751,6 +751,38 @@ class DeseqDataSet:
         self.uns["rlog_beta_prior_var"] = bpv
         return self.layers["rlog_counts"]
 
+    def _transformed_layer(self, layer, what):
+        if layer not in self.layers:
+            raise KeyError(f"{what}: no layer {layer!r} (run vst() or rlog() first; available: {sorted(self.layers.available())}).")
+        x = np.asarray(self.layers[layer])
+        if x.shape != (self.n_obs, self.n_vars):
+            raise ValueError(f"{what}: layer {layer!r} has shape {x.shape}, not samples x genes = {(self.n_obs, self.n_vars)}.")
+        return x
+
+    def pca(self, layer: str = "vst_counts", ntop=500, n_components=None):
+        """Sample PCA of a transformed layer (DESeq2's ``plotPCA(returnData = TRUE)``): the principal
+        components of the ``ntop`` most variable genes.  Returns a ``pydeseq2_amd.pca.PcaResult`` whose ``scores`` is a
+        DataFrame indexed by the sample names with columns ``PC1`` ...; ``genes`` holds the names of the genes used, in
+        order of decreasing variance.  Nothing is stored on the data set.  KeyError: no such layer; ValueError: a layer
+        of another shape, fewer than two samples, ``ntop < 1``, ``n_components`` outside 1 ... min(N, K), a non-finite
+        row variance."""
+        from . import pca as _pca
+
+        x = self._transformed_layer(layer, "pca()")
+        _pca.check_pca_args(self.n_obs, self.n_vars, ntop, n_components)
+        r = _pca.pca(self._pipe, x, ntop=ntop, n_components=n_components)
+        r.scores = pd.DataFrame(r.scores, index=self.obs_names, columns=[f"PC{i + 1}" for i in range(r.scores.shape[1])])
+        r.genes = self.var_names[r.genes]
+        return r
+
+    def sample_distances(self, layer: str = "vst_counts"):
+        """Euclidean sample-to-sample distances over all genes of a transformed layer (R's ``dist(t(assay(vsd)))``): an
+        N x N DataFrame labelled by the sample names.  Nothing is stored on the data set."""
+        from . import pca as _pca
+
+        x = self._transformed_layer(layer, "sample_distances()")
+        return pd.DataFrame(_pca.sample_distances(self._pipe, x), index=self.obs_names, columns=self.obs_names)
+
     @property
     def non_zero_genes(self):
         return self.var_names[np.asarray(self.var["non_zero"], dtype=bool)]

@@ -672,6 +672,44 @@ int dsq_dev_ash(dsq_ctx* ctx, const double* d_lfc, const double* d_se, int G, in
     return DSQ_OK;
 }
 
+int dsq_dev_row_meanvar(dsq_ctx* ctx, const double* d_x, int layout, int N, int G, int ld, double* d_mean, double* d_var) {
+    DSQ_CHECK_ARG(N >= 1, "N: at least one sample");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(layout == DSQ_SAMPLE_MAJOR || layout == DSQ_GENE_MAJOR, "layout: DSQ_SAMPLE_MAJOR or DSQ_GENE_MAJOR");
+    DSQ_CHECK_ARG(ld >= (layout == DSQ_GENE_MAJOR ? N : G), "ld is smaller than a row of the layout");
+    DSQ_CHECK_ARG(d_mean != nullptr, "d_mean is null");
+    if (G == 0) return DSQ_OK;
+    DSQ_CHECK_ARG(d_x != nullptr, "d_x is null");
+    DSQ_HIP(dsq::launch_row_meanvar(ctx->stream, d_x, layout, N, G, ld, d_mean, d_var));
+    return DSQ_OK;
+}
+
+size_t dsq_sample_gram_work_doubles(int N, int K) { return dsq::sample_gram_work_doubles(N, K); }
+
+int dsq_dev_sample_gram(dsq_ctx* ctx, const double* d_x, int layout, int N, int G, int ld, const int32_t* d_sel, int K,
+                        const double* d_mean, double* d_work, double* d_S, int lds) {
+    DSQ_CHECK_ARG(N >= 1, "N: at least one sample");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(K >= 0, "K is negative");
+    DSQ_CHECK_ARG(d_sel != nullptr || K <= G, "K is larger than G without a gene list");
+    DSQ_CHECK_ARG(layout == DSQ_SAMPLE_MAJOR || layout == DSQ_GENE_MAJOR, "layout: DSQ_SAMPLE_MAJOR or DSQ_GENE_MAJOR");
+    DSQ_CHECK_ARG(ld >= (layout == DSQ_GENE_MAJOR ? N : G), "ld is smaller than a row of the layout");
+    DSQ_CHECK_ARG(lds >= N, "lds is smaller than N");
+    DSQ_CHECK_ARG(d_S != nullptr, "d_S is null");
+    const int k = G == 0 ? 0 : K;  // no gene to take: S = 0
+    DSQ_CHECK_ARG(k == 0 || (d_x != nullptr && d_work != nullptr), "d_x or d_work is null");
+    DSQ_HIP(dsq::launch_sample_gram(ctx->stream, d_x, layout, N, ld, d_sel, k, d_mean, d_work, d_S, lds));
+    return DSQ_OK;
+}
+
+int dsq_dev_gram_dist(dsq_ctx* ctx, const double* d_S, int N, int lds, double* d_D, int ldd) {
+    DSQ_CHECK_ARG(N >= 1, "N: at least one sample");
+    DSQ_CHECK_ARG(lds >= N && ldd >= N, "lds or ldd is smaller than N");
+    DSQ_CHECK_ARG(d_S != nullptr && d_D != nullptr, "d_S or d_D is null");
+    DSQ_HIP(dsq::launch_gram_dist(ctx->stream, d_S, N, lds, d_D, ldd));
+    return DSQ_OK;
+}
+
 int dsq_dev_gather_rows_f64(dsq_ctx* ctx, const double* d_src, int ld, const int32_t* d_idx, int n_idx,
                             int ncols, double* d_dst) {
     DSQ_HIP(dsq::launch_gather_rows_f64(ctx->stream, d_src, ld, d_idx, n_idx, ncols, d_dst));

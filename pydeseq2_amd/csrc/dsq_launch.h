@@ -338,6 +338,14 @@ hipError_t launch_ash_fit(hipStream_t st, const double* lfc, const double* se, i
                           double* kkt, double* loglik);
 hipError_t launch_ash_post(hipStream_t st, const double* lfc, const double* se, int G, int ldg, int K, const double* sd,
                            const int32_t* m, int ldm, const double* pi, double* post_mean, double* post_sd, double* lfsr);
+// ---- dsq_k_gram.hip: sample PCA / sample distances of a transformed matrix (dsq_gram.h): per-gene means and variances
+// (layout as dsq_layout, var may be null), the centred N x N Gram over a gene list (work: sample_gram_work_doubles) and
+// the Euclidean distances from it
+hipError_t launch_row_meanvar(hipStream_t st, const double* x, int layout, int N, int G, int ld, double* mean, double* var);
+size_t sample_gram_work_doubles(int N, int K);
+hipError_t launch_sample_gram(hipStream_t st, const double* x, int layout, int N, int ld, const int32_t* sel, int K,
+                              const double* mean, double* work, double* S, int lds_S);
+hipError_t launch_gram_dist(hipStream_t st, const double* S, int N, int lds_S, double* D, int ldd);
 hipError_t launch_cooks(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* mu,
                         const double* hat, const int32_t* cell_offsets, const int32_t* cell_index,
                         int n_cells, int whole, int max_cell, const uint8_t* flags, int N, int G,

@@ -1591,6 +1591,19 @@ class DeseqPipeline:
 
         return ash(self, lfc, se)
 
+    def pca(self, x, ntop=500, n_components=None):
+        """Sample PCA of a transformed N x G matrix (DESeq2's plotPCA; csrc/dsq_gram.h) on this pipeline's
+        device: pydeseq2_amd.pca.pca.  (Single process: the gene-sharded pipeline has no counterpart.)"""
+        from .pca import pca
+
+        return pca(self, x, ntop=ntop, n_components=n_components)
+
+    def sample_distances(self, x, genes=None):
+        """Euclidean sample-to-sample distances of a transformed N x G matrix (R's dist): pydeseq2_amd.pca.sample_distances."""
+        from .pca import sample_distances
+
+        return sample_distances(self, x, genes=genes)
+
     def close(self):
         """Release the pooled device buffers."""
         if getattr(self, "_side_pending", False) or getattr(self, "_lfc_forked", False):
