@@ -58,6 +58,15 @@ struct LfcEpilogue {
     WaldOut wald;
 };
 
+// LDS copies of the per-sample operands (IrlsOperands<true>); npad = N rounded up to 16
+struct alignas(16) SfLsf { double sf, lsf; };
+struct IrlsStage {
+    const SfLsf* sl = nullptr;    // [npad] size factor and its logarithm
+    const int32_t* y = nullptr;   // [npad] this wave's counts
+    const uint8_t* cf = nullptr;  // [npad] cell index (<= 3) | Cook's flags << 2
+    const double* lgi = nullptr;  // [kLgammaIntN] kLgammaInt
+};
+
 struct IrlsArgs {
     const int32_t* y;     // [N]
     const double* sf;     // [N]
@@ -71,6 +80,50 @@ struct IrlsArgs {
     const CellDesign* cells = nullptr;  // CELL instantiations (designs with <= 64 distinct rows)
     const double* pinvc = nullptr;      // [C][P] column of (X^T X)^-1 X^T of each cell (LDS; k_irls_row, full rank)
     void* cell_ws = nullptr;            // this wave's CellWork<P>
+    IrlsStage stg;                      // STG instantiations: the operands above, staged in LDS
+};
+
+// The operands of one sample as the sample loops of irls_init, irls_sweep_cs and irls_finish_cs fetch them.  STG = false:
+// through the pointers of IrlsArgs, whose address space the compiler does not know (global memory, or LDS rebound at
+// run time).  STG = true (k_irls<P, 2 | 3, true>): everything a trip reads lies in LDS behind typed pointers - ds_read
+// with immediate offsets off one 32-bit index, and no load from global memory that a trip would have to wait for
+// together with the stores of the trip before it.
+template <bool STG>
+struct IrlsOperands {
+    const IrlsArgs& A;
+    const uint8_t* flags;  // LfcEpilogue::flags (STG: unused, the bits ride on the cell index)
+    DSQ_HD IrlsOperands(const IrlsArgs& A_, const uint8_t* flags_ = nullptr) : A(A_), flags(flags_) {}
+    DSQ_HD int y(int n) const {
+        if constexpr (STG) return DSQ_AS_LDS(int32_t, A.stg.y)[n];
+        else return A.y[n];
+    }
+    DSQ_HD void sf_lsf(int n, double& sfn, double& lsfn) const {
+        if constexpr (STG) {
+            const SfLsf v = DSQ_AS_LDS(SfLsf, A.stg.sl)[n];
+            sfn = v.sf;
+            lsfn = v.lsf;
+        } else {
+            sfn = A.sf[n];
+            lsfn = (A.lsf != nullptr) ? A.lsf[n] : flog(sfn);
+        }
+    }
+    DSQ_HD double sf(int n) const {
+        if constexpr (STG) return DSQ_AS_LDS(SfLsf, A.stg.sl)[n].sf;
+        else return A.sf[n];
+    }
+    // cell index and Cook's flags of a sample: cf = cell | flags << 2 (STG: one byte read)
+    DSQ_HD int cf(int n, bool want_flags) const {
+        if constexpr (STG) return DSQ_AS_LDS(uint8_t, A.stg.cf)[n];
+        else return A.cells->cell_of[n] | (want_flags ? (int)flags[n] << 2 : 0);
+    }
+    DSQ_HD int cell(int n) const {
+        if constexpr (STG) return DSQ_AS_LDS(uint8_t, A.stg.cf)[n] & 3;
+        else return A.cells->cell_of[n];
+    }
+    DSQ_HD double lgamma_int(int i) const {
+        if constexpr (STG) return DSQ_AS_LDS(double, A.stg.lgi)[i];
+        else return kLgammaInt[i];
+    }
 };
 
 // sweep: mu(beta) clamped, S = sum (y+a) log(a+mu) - y log mu, M = X^T W X, r = X^T W z
@@ -263,11 +316,56 @@ DSQ_HD double cell_select(int cell, const double (&v)[CS]) {
     return r;
 }
 
-template <class Wv, int P, int CS>
+// A wave-uniform value held in vector registers, where a per-lane select takes it as it is (from scalar registers
+// every select costs a v_mov per half and trip first).
+DSQ_HD double in_vgpr(double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
+
+// s0[c] += v0, s1[c] += v1 for the sample's cell c.  MASKED (two cells, device): each cell's two adds run under that
+// cell's lane mask, and the other cell's sums are left alone - adding +0.0 to them, as the selects below do, gives the
+// same bits (a sum starts at +0.0, and x + 0.0 == x for every x but -0.0, which no sum can become: +0.0 + -0.0 = +0.0).
+// v0 and v1 are operands of the add instructions themselves: rounded products, as they are in front of a select (no
+// fused multiply-add into the sums).  Written as instructions: every C++ form of the two branches comes back from the
+// compiler as eight v_cndmask (or, through a merged temporary, as more).  The lanes beyond N stay off: both masks are
+// taken from the EXEC the block is entered with, which it restores.
+template <int CS, bool MASKED>
+DSQ_HD void cell_add2(int cell, double (&s0)[CS], double v0, double (&s1)[CS], double v1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (CS == 2 && MASKED) {
+        unsigned long long entered;
+        asm volatile(
+            "s_mov_b64 %4, exec\n\t"
+            "v_cmp_eq_u32_e32 vcc, 0, %7\n\t"
+            "s_and_b64 exec, %4, vcc\n\t"
+            "v_add_f64 %0, %0, %5\n\t"
+            "v_add_f64 %1, %1, %6\n\t"
+            "s_andn2_b64 exec, %4, vcc\n\t"
+            "v_add_f64 %2, %2, %5\n\t"
+            "v_add_f64 %3, %3, %6\n\t"
+            "s_mov_b64 exec, %4"
+            : "+v"(s0[0]), "+v"(s1[0]), "+v"(s0[1]), "+v"(s1[1]), "=&s"(entered)
+            : "v"(v0), "v"(v1), "v"(cell)
+            : "vcc", "scc");
+        return;
+    }
+#endif
+#pragma unroll
+    for (int c = 0; c < CS; ++c) {
+        s0[c] += (cell == c) ? v0 : 0.0;
+        s1[c] += (cell == c) ? v1 : 0.0;
+    }
+}
+
+template <class Wv, int P, int CS, bool STG = false>
 DSQ_HD void irls_sweep_cs(const IrlsArgs& A, const double (&beta)[P], double a, double& S,
                           double (&M)[Tri<P>::N], double (&r)[P], double (&e_c)[CS]) {
     constexpr int T = Tri<P>::N;
     const CellDesign& D = *A.cells;
+    const IrlsOperands<STG> ops(A);
     const auto Xc_ = DSQ_AS_LDS(double, D.Xc);
     const auto XX_ = DSQ_AS_LDS(double, D.XX);
     double eta_c[CS], sw[CS], swz[CS];
@@ -278,33 +376,31 @@ DSQ_HD void irls_sweep_cs(const IrlsArgs& A, const double (&beta)[P], double a, 
 #pragma unroll
             for (int j = 0; j < P; ++j) eta += Xc_[c * P + j] * beta[j];
         }
-        eta_c[c] = Wv::uniform(eta);
-        e_c[c] = Wv::uniform(exp(eta));
+        // (STG: every lane holds the same two numbers anyway; see in_vgpr)
+        eta_c[c] = STG ? in_vgpr(eta) : Wv::uniform(eta);
+        e_c[c] = STG ? in_vgpr(exp(eta)) : Wv::uniform(exp(eta));
         sw[c] = 0.0;
         swz[c] = 0.0;
     }
     double s = 0.0;
     const double lmin = log(A.min_mu);
+    const double min_mu = STG ? in_vgpr(A.min_mu) : A.min_mu;
     DSQ_PHASE(3);
     for (int n = Wv::lane(); n < A.N; n += Wv::W) {
-        const double yv = (double)A.y[n];
-        const double sfn = A.sf[n];
-        const int cell = D.cell_of[n];
+        const double yv = (double)ops.y(n);
+        double sfn, lsfn;
+        ops.sf_lsf(n, sfn, lsfn);
+        const int cell = ops.cell(n);
         const double eta = cell_select<CS>(cell, eta_c);
         const double mu_raw = sfn * cell_select<CS>(cell, e_c);
-        const bool clamped = !(mu_raw > A.min_mu);
-        const double mu = clamped ? A.min_mu : mu_raw;
-        const double lsfn = (A.lsf != nullptr) ? A.lsf[n] : flog(sfn);
+        const bool clamped = !(mu_raw > min_mu);
+        const double mu = clamped ? min_mu : mu_raw;
         const double lmu = clamped ? lmin : eta + lsfn;
         s += (yv + a) * flog_t(a + mu) - yv * lmu;
         const double rd = frcp(1.0 + mu * A.disp);  // (see irls_sweep)
         const double w = mu * rd;
         const double wz = (mu * (clamped ? lmin - lsfn : eta) + (yv - mu)) * rd;
-#pragma unroll
-        for (int c = 0; c < CS; ++c) {
-            sw[c] += (cell == c) ? w : 0.0;
-            swz[c] += (cell == c) ? wz : 0.0;
-        }
+        cell_add2<CS, STG>(cell, sw, w, swz, wz);
     }
     DSQ_PHASE(4);
     S = Wv::sum(s);
@@ -327,7 +423,7 @@ DSQ_HD void irls_sweep_cs(const IrlsArgs& A, const double (&beta)[P], double a, 
     }
 }
 
-template <class Wv, int P, int CS>
+template <class Wv, int P, int CS, bool STG = false>
 DSQ_HD void irls_finish_cs(const IrlsArgs& A, const double (&beta)[P], double (&M)[Tri<P>::N],
                            const double (&e_c)[CS], double* mu_out, double* H_out, LfcEpilogue* E = nullptr) {
     constexpr int T = Tri<P>::N;
@@ -358,9 +454,11 @@ DSQ_HD void irls_finish_cs(const IrlsArgs& A, const double (&beta)[P], double (&
         }
     }
     CooksAcc<Wv> acc(want_cooks ? E->robust_disp : 0.0, want_cooks ? E->cutoff : 0.0, P);
+    const IrlsOperands<STG> ops(A, want_cooks ? E->flags : nullptr);
     for (int n = Wv::lane(); n < A.N; n += Wv::W) {
-        const int cell = D.cell_of[n];
-        const double mu_raw = A.sf[n] * cell_select<CS>(cell, e_c);
+        const int cf = ops.cf(n, want_cooks);
+        const int cell = cf & 3;
+        const double mu_raw = ops.sf(n) * cell_select<CS>(cell, e_c);
         if (mu_out != nullptr) mu_out[n] = mu_raw;
         double w = 0.0;
         const bool have_w = H_out != nullptr || want_cooks;
@@ -370,7 +468,7 @@ DSQ_HD void irls_finish_cs(const IrlsArgs& A, const double (&beta)[P], double (&
             const double h = w * cell_select<CS>(cell, q_c);  // (sqrt(w) q sqrt(w) of utils.py:430-433, to an ulp)
             if (H_out != nullptr) H_out[n] = h;
             if (want_cooks) {
-                const double ck = acc.add(n, (double)A.y[n], mu_raw, h, E->flags[n]);
+                const double ck = acc.add(n, (double)ops.y(n), mu_raw, h, cf >> 2);
                 if (E->cooks_row != nullptr) E->cooks_row[n] = ck;
             }
         }
@@ -382,7 +480,17 @@ DSQ_HD void irls_finish_cs(const IrlsArgs& A, const double (&beta)[P], double (&
             for (int c = 0; c < CS; ++c) swu[c] += (cell == c) ? wu : 0.0;
         }
     }
-    if (want_cooks) E->cooks = acc.finish(A.y, A.N);
+    if (want_cooks) {
+        if constexpr (STG) {  // (finish() with the counts read where they are staged)
+            E->cooks = acc.finish_counted(A.N, [&](int yref) {
+                int above = 0;
+                for (int n = Wv::lane(); n < A.N; n += Wv::W) above += (ops.y(n) > yref) ? 1 : 0;
+                return above;
+            });
+        } else {
+            E->cooks = acc.finish(A.y, A.N);
+        }
+    }
     if (want_wald) {
         double Mw[T];
 #pragma unroll
@@ -411,8 +519,9 @@ struct IrlsOut {
 // count k once, counts >= 64 take the Stirling formula), log(y!) from the 256-entry table.  cst only
 // enters the deviance's denominator |dev| + 0.1 (it cancels in dev - old_dev), so ulp-level
 // differences from scipy's gammaln are immaterial.
-template <class Wv, int P>
+template <class Wv, int P, bool STG = false>
 DSQ_HD void irls_init(const IrlsArgs& A, double a, double (&b0)[P], double& cst) {
+    const IrlsOperands<STG> ops(A);
 #pragma unroll
     for (int j = 0; j < P; ++j) b0[j] = 0.0;
     double lga, dga_unused, tab_dl, tab_dd;
@@ -422,7 +531,17 @@ DSQ_HD void irls_init(const IrlsArgs& A, double a, double (&b0)[P], double& cst)
     for (int base = 0; base < A.N; base += Wv::W) {  // wave-uniform trip count (cross-lane memo reads)
         const int n = base + Wv::lane();
         const bool valid = n < A.N;
-        const int yi = valid ? A.y[n] : 0;
+        // STG: the pseudo-inverse's entries are the trip's only loads from global memory; issued first (index clamped),
+        // they return while the LDS operands are read and the memo is consulted
+        double pinv[P] = {};
+        if constexpr (STG) {
+            if (A.full_rank) {
+                const int nc = valid ? n : A.N - 1;
+#pragma unroll
+                for (int j = 0; j < P; ++j) pinv[j] = A.pinvXt[j * A.ldx + nc];
+            }
+        }
+        const int yi = valid ? ops.y(n) : 0;
         const double yv = (double)yi;
         const bool in_tab = yi < Wv::W;
         double dl = Wv::from_lane(tab_dl, in_tab ? yi : 0);
@@ -432,7 +551,7 @@ DSQ_HD void irls_init(const IrlsArgs& A, double a, double (&b0)[P], double& cst)
             dl = in_tab ? dl : dl2;
         }
         const bool in_fact = yi < kLgammaIntN;
-        double lf = kLgammaInt[in_fact ? yi : 0];
+        double lf = ops.lgamma_int(in_fact ? yi : 0);
         if (Wv::any(!in_fact)) {
             const double z = in_fact ? 300.0 : yv + 1.0;  // z >= 257: the table logarithm and the truncated tail
             const double big = (z - 0.5) * flog_t(z) - z + kHalfLog2Pi + stirling_tail_big(frcp(z));
@@ -444,11 +563,14 @@ DSQ_HD void irls_init(const IrlsArgs& A, double a, double (&b0)[P], double& cst)
                 // log(y / sf + 0.1) (utils.py:351) with the lean log and a reciprocal (<= 1 ulp each; the sum over
                 // the samples runs in another order than numpy's anyway): the library log + IEEE division here
                 // were a sixth of the kernel
-                const double ly = flog_t(yv * frcp(A.sf[n]) + 0.1);
+                const double ly = flog_t(yv * frcp(ops.sf(n)) + 0.1);
 #pragma unroll
-                for (int j = 0; j < P; ++j) b0[j] += A.pinvXt[j * A.ldx + n] * ly;
+                for (int j = 0; j < P; ++j) {
+                    if constexpr (STG) b0[j] += pinv[j] * ly;
+                    else b0[j] += A.pinvXt[j * A.ldx + n] * ly;
+                }
             } else {
-                b0[0] += log(yv / A.sf[n]);
+                b0[0] += log(yv / ops.sf(n));
             }
         }
     }
@@ -732,9 +854,10 @@ DSQ_HD void irls_finish_cell(const IrlsArgs& A, const double (&beta)[P], double 
 
 // beta (out), mu_out[N] = UNclamped sf*exp(X beta), H_out[N] hat diagonal (either may be null).
 // When IRLS diverges nothing is written and out.fallback = 1.
+// STG (CELL >= 2 only): the per-sample operands are read from their LDS copies (IrlsOperands<true>, A.stg).
 // CELL: 0 general design, 1 per-cell sums in LDS (5 .. 64 cells), 2 per-cell sums in registers (<= kSmallCells),
 // 3 the same for at most two cells (the two-group comparison: half the selects and accumulators per sample)
-template <class Wv, int P, int CELL = 0>
+template <class Wv, int P, int CELL = 0, bool STG = false>
 DSQ_HD IrlsOut irls_gene(const IrlsArgs& A, double (&beta)[P], double* mu_out, double* H_out,
                          LfcEpilogue* E = nullptr) {
     constexpr int T = Tri<P>::N;
@@ -747,7 +870,7 @@ DSQ_HD IrlsOut irls_gene(const IrlsArgs& A, double (&beta)[P], double* mu_out, d
         if (A.pinvc != nullptr) irls_init_cell<Wv, P>(A, a, beta, cst);
         else irls_init<Wv, P>(A, a, beta, cst);
     } else {
-        irls_init<Wv, P>(A, a, beta, cst);
+        irls_init<Wv, P, STG>(A, a, beta, cst);
     }
     const double nlogterm = A.N * a * log(A.disp);
     double M[T], r[P], S;
@@ -759,7 +882,7 @@ DSQ_HD IrlsOut irls_gene(const IrlsArgs& A, double (&beta)[P], double* mu_out, d
     auto sweep = [&]() {
         DSQ_PHASE(2);
         if constexpr (CELL == 1) irls_sweep_cell<Wv, P, !kRowSolve>(A, beta, a, S, M, r);
-        else if constexpr (CELL >= 2) irls_sweep_cs<Wv, P, CS>(A, beta, a, S, M, r, e_c);
+        else if constexpr (CELL >= 2) irls_sweep_cs<Wv, P, CS, STG>(A, beta, a, S, M, r, e_c);
         else irls_sweep<Wv, P>(A, beta, a, S, M, r);
         DSQ_PHASE(5);
     };
@@ -812,7 +935,7 @@ DSQ_HD IrlsOut irls_gene(const IrlsArgs& A, double (&beta)[P], double* mu_out, d
         Wv::sync();  // (the finish reuses ent)
     }
     if constexpr (CELL == 1) irls_finish_cell<Wv, P>(A, beta, M, mu_out, H_out, E);
-    else if constexpr (CELL >= 2) irls_finish_cs<Wv, P, CS>(A, beta, M, e_c, mu_out, H_out, E);
+    else if constexpr (CELL >= 2) irls_finish_cs<Wv, P, CS, STG>(A, beta, M, e_c, mu_out, H_out, E);
     else irls_finish<Wv, P>(A, beta, M, mu_out, H_out, E);
     return out;
 }

@@ -20,7 +20,16 @@ __device__ unsigned long long g_phase_total_irls[16];
 #endif
 constexpr int irls_min_waves(int p) { return p <= 2 ? DSQ_IRLS_WAVES_P2 : (p <= 5 ? 1 : 2); }
 
-template <int P, int CELL>
+// LDS of the typed staging (STG) of the few-cell kernels, after the log table: kLgammaInt, per sample the size factor
+// with its logarithm (16 B) and one byte of cell index and Cook's flags, per wave and sample a count (4 B), then the
+// cells' tables.  N = 1000, two cells: 35 392 B + the 2 KB log table - four workgroups per CU.
+constexpr size_t irls_stg_bytes(int N, size_t tables) {
+    return kLgammaIntN * sizeof(double) + (size_t)((N + 15) & ~15) * (sizeof(SfLsf) + 1 + 4 * kWavesPerBlock) + tables;
+}
+
+// STG (CELL 2 and 3 only): staging is a property of the instantiation and the sample loops read LDS-typed operands
+// (IrlsOperands<true>); otherwise `stage` decides at run time and the loops go through generic pointers.
+template <int P, int CELL, bool STG = false>
 __global__ __launch_bounds__(kBlock, CELL == 1 ? cell_min_waves(P) : irls_min_waves(P)) void k_irls(const int32_t* __restrict__ y, int ldn,
                                                  const double* __restrict__ sf, const double* __restrict__ lsf,
                                                  const double* __restrict__ Xt,
@@ -45,9 +54,34 @@ __global__ __launch_bounds__(kBlock, CELL == 1 ? cell_min_waves(P) : irls_min_wa
         }
         if (!any) return;
     }
+    static_assert(!STG || CELL >= 2, "typed staging: the few-cell kernels only");
     log_tab_fill();  // the table of flog_t (dsq_math.h); the barrier below covers it
     double* lds_next = irls_lds;
-    if (CELL) {  // the cells' tables once per workgroup into LDS (read by every entry-parallel rebuild)
+    IrlsStage stg;
+    if constexpr (STG) {
+        constexpr int T = Tri<P>::N;
+        const int npad = (N + 15) & ~15;
+        double* s_lgi = irls_lds;
+        SfLsf* s_sl = (SfLsf*)(s_lgi + kLgammaIntN);
+        int32_t* s_y = (int32_t*)(s_sl + npad) + (size_t)w * npad;
+        uint8_t* s_cf = (uint8_t*)((int32_t*)(s_sl + npad) + (size_t)kWavesPerBlock * npad);
+        double* sXX = (double*)(s_cf + npad);
+        double* sXc = sXX + ex.cells.C * T;
+        for (int i = threadIdx.x; i < kLgammaIntN; i += kBlock) s_lgi[i] = kLgammaInt[i];
+        for (int i = threadIdx.x; i < ex.cells.C * T; i += kBlock) sXX[i] = ex.cells.XX[i];
+        for (int i = threadIdx.x; i < ex.cells.C * P; i += kBlock) sXc[i] = ex.cells.Xc[i];
+        for (int n = threadIdx.x; n < N; n += kBlock) {
+            const double sfn = sf[n];
+            s_sl[n].sf = sfn;
+            s_sl[n].lsf = lsf != nullptr ? lsf[n] : flog(sfn);  // (what the unstaged loop computes per trip)
+            s_cf[n] = (uint8_t)(ex.cells.cell_of[n] | (ex.flags != nullptr ? ex.flags[n] << 2 : 0));
+        }
+        const int32_t* yg = y + (size_t)(g < G ? g : G - 1) * ldn;
+        for (int n = threadIdx.x & 63; n < N; n += 64) s_y[n] = yg[n];
+        ex.cells.XX = sXX;
+        ex.cells.Xc = sXc;
+        stg.sl = s_sl; stg.y = s_y; stg.cf = s_cf; stg.lgi = s_lgi;
+    } else if (CELL) {  // the cells' tables once per workgroup into LDS (read by every entry-parallel rebuild)
         constexpr int T = Tri<P>::N;
         double* sXX = lds_next;
         double* sXc = sXX + ex.cells.C * T;
@@ -62,7 +96,7 @@ __global__ __launch_bounds__(kBlock, CELL == 1 ? cell_min_waves(P) : irls_min_wa
     // of this kernel were s_waitcnt).  stage: they are copied into LDS once - the shared vectors per workgroup, the
     // counts per wave - and the sweeps run from there.
     const int32_t* yrow = y + (size_t)(g < G ? g : G - 1) * ldn;
-    if (stage) {
+    if (!STG && stage) {
         const int npad = (N + 15) & ~15;
         double* s_sf = lds_next;
         double* s_lsf = s_sf + npad;
@@ -94,10 +128,11 @@ __global__ __launch_bounds__(kBlock, CELL == 1 ? cell_min_waves(P) : irls_min_wa
     A.disp = disp[g]; A.min_mu = min_mu; A.beta_tol = beta_tol; A.min_beta = min_beta;
     A.max_beta = max_beta; A.maxiter = maxiter; A.full_rank = full_rank != 0;
     if (CELL) { A.cells = &ex.cells; A.cell_ws = CELL == 1 ? (void*)&cellw[w] : nullptr; }
+    A.stg = stg;
     LfcEpilogue E;
     epilogue_begin(E, ex, g, ldn);
     double b[P];
-    const IrlsOut o = irls_gene<DeviceWave, P, CELL>(A, b, mu ? mu + (size_t)g * ldn : nullptr,
+    const IrlsOut o = irls_gene<DeviceWave, P, CELL, STG>(A, b, mu ? mu + (size_t)g * ldn : nullptr,
                                                      hat ? hat + (size_t)g * ldn : nullptr, &E);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -482,6 +517,12 @@ static hipError_t launch_irls_mix(hipStream_t st, const int32_t* y, int ldn, con
     }
 }
 
+// one of the few-cell kernels; lds__: its dynamic LDS
+#define DSQ_IRLS_CS_LAUNCH(P__, CELL__, STG__, lds__)                                                                 \
+    hipLaunchKernelGGL((k_irls<P__, CELL__, STG__>), grid, block, lds__, st, y, ldn, sf, lsf, Xt, pinvXt, ldx, N, G,  \
+                       full_rank, disp, min_mu, beta_tol, min_beta, max_beta, maxiter, beta, mu, hat, conv, iters,     \
+                       fb_count, fb_list, ex, 0)
+
 hipError_t launch_irls(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* lsf,
                        const double* Xt,
                        const double* pinvXt, int ldx, int N, int G, int P_, int full_rank,
@@ -506,22 +547,21 @@ hipError_t launch_irls(hipStream_t st, const int32_t* y, int ldn, const double* 
     // LDS staging of the per-sample vectors (sf, log sf: 16 B; cell index: 4 B) and the waves' count rows (4 B each)
     const int npad = (N + 15) & ~15;
     const size_t stage_bytes = (size_t)npad * (16 + 4 + 4 * kWavesPerBlock);
+    constexpr size_t kIrlsStageLimit = 48 * 1024;  // dynamic LDS of a staged launch
     static const bool allow_stage = getenv("DSQ_IRLS_NO_STAGE") == nullptr;
     if (ex.cells.C > 0 && ex.cells.C <= kSmallCells && P_ <= 4) {
         // <= 4 distinct design rows (two-group designs): per-cell exponentials and weight sums in registers
         DSQ_DISPATCH_P(P_, {
             if constexpr (P <= 4) {
                 const size_t tables = (size_t)ex.cells.C * (Tri<P>::N + P) * sizeof(double);
-                const int stage = allow_stage && tables + stage_bytes <= 48 * 1024;
-                if (ex.cells.C <= 2 && P <= 2)
-                    hipLaunchKernelGGL((k_irls<(P <= 2 ? P : 1), 3>), grid, block, tables + (stage ? stage_bytes : 0),
-                                       st, y, ldn, sf, lsf, Xt, pinvXt, ldx, N, G, full_rank, disp, min_mu, beta_tol,
-                                       min_beta, max_beta, maxiter, beta, mu, hat, conv, iters, fb_count, fb_list, ex,
-                                       stage);
-                else
-                    hipLaunchKernelGGL((k_irls<P, 2>), grid, block, tables + (stage ? stage_bytes : 0), st, y, ldn,
-                                       sf, lsf, Xt, pinvXt, ldx, N, G, full_rank, disp, min_mu, beta_tol, min_beta,
-                                       max_beta, maxiter, beta, mu, hat, conv, iters, fb_count, fb_list, ex, stage);
+                const size_t staged = irls_stg_bytes(N, tables);
+                const bool stage = allow_stage && staged <= kIrlsStageLimit;
+                constexpr int PP = P <= 2 ? P : 1;  // (CELL 3 exists for P <= 2)
+                const bool two = ex.cells.C <= 2 && P <= 2;
+                if (two && stage) DSQ_IRLS_CS_LAUNCH(PP, 3, true, staged);
+                else if (two) DSQ_IRLS_CS_LAUNCH(PP, 3, false, tables);
+                else if (stage) DSQ_IRLS_CS_LAUNCH(P, 2, true, staged);
+                else DSQ_IRLS_CS_LAUNCH(P, 2, false, tables);
             }
         })
     } else if (irls_takes_rows(N, P_, ex.cells.C) && G >= irls_row_min_genes()) {
@@ -539,14 +579,14 @@ hipError_t launch_irls(hipStream_t st, const int32_t* y, int ldn, const double* 
         DSQ_DISPATCH_P(P_, {
             if constexpr (P >= 3) {
                 const size_t tables = (size_t)ex.cells.C * (Tri<P>::N + P) * sizeof(double);
-                const int stage = allow_stage && tables + stage_bytes <= 48 * 1024;
+                const int stage = allow_stage && tables + stage_bytes <= kIrlsStageLimit;
                 hipLaunchKernelGGL((k_irls<P, 1>), grid, block, tables + (stage ? stage_bytes : 0), st, y, ldn, sf,
                                    lsf, Xt, pinvXt, ldx, N, G, full_rank, disp, min_mu, beta_tol, min_beta, max_beta,
                                    maxiter, beta, mu, hat, conv, iters, fb_count, fb_list, ex, stage);
             }
         })
     } else {
-        const int stage = allow_stage && stage_bytes <= 48 * 1024;
+        const int stage = allow_stage && stage_bytes <= kIrlsStageLimit;
         DSQ_DISPATCH_P(P_, hipLaunchKernelGGL((k_irls<P, 0>), grid, block, stage ? stage_bytes : 0, st, y, ldn, sf,
                                               lsf, Xt, pinvXt, ldx, N, G, full_rank, disp, min_mu, beta_tol, min_beta,
                                               max_beta, maxiter, beta, mu, hat, conv, iters, fb_count, fb_list, ex,
