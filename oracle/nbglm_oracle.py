@@ -1112,6 +1112,35 @@ def nbinom_fn(beta, X, counts, size, offset, prior_no_shrink_scale, prior_scale,
     return prior - nll
 
 
+def nbinom_grad(beta, X, counts, size, offset, prior_no_shrink_scale, prior_scale, shrink_index=1):
+    """Gradient of ``nbinom_fn`` as utils.nbinomGLM's ``df`` forms it (utils.py:1075-1089), unscaled."""
+    p = X.shape[-1]
+    shrink_mask = np.zeros(p)
+    shrink_mask[shrink_index] = 1
+    no_shrink_mask = np.ones(p) - shrink_mask
+    xbeta = X @ beta
+    d_neg_prior = (beta * no_shrink_mask / prior_no_shrink_scale**2
+                   + 2 * beta * shrink_mask / (prior_scale**2 + beta[shrink_index] ** 2))
+    d_nll = (counts - (counts + size) / (1 + size * np.exp(-xbeta - offset))) @ X
+    return d_neg_prior - d_nll
+
+
+def nbinom_hess(beta, X, counts, size, offset, prior_no_shrink_scale, prior_scale, shrink_index=1):
+    """utils.nbinomGLM's ``ddf`` with c = 1 (utils.py:1091-1110).  Kept as in the reference: ``h`` is already a diagonal
+    matrix, so ``np.diag(h)`` is the VECTOR of prior curvatures and broadcasting adds h_j to every row of column j."""
+    p = X.shape[-1]
+    shrink_mask = np.zeros(p)
+    shrink_mask[shrink_index] = 1
+    no_shrink_mask = np.ones(p) - shrink_mask
+    xbeta = X @ beta
+    e = np.exp(xbeta + offset)
+    frac = (counts + size) * size * e / (size + e) ** 2
+    h11 = 1 / prior_no_shrink_scale**2
+    h22 = 2 * (prior_scale**2 - beta[shrink_index] ** 2) / (prior_scale**2 + beta[shrink_index] ** 2) ** 2
+    h = np.diag(no_shrink_mask * h11 + shrink_mask * h22)
+    return (X.T * frac) @ X + np.diag(h)
+
+
 def grid_fit_shrink_beta(counts, offset, X, size, prior_no_shrink_scale, prior_scale, scale_cnst,
                          grid_length=60, min_beta=-30, max_beta=30):
     """Two-level 2-D grid search (grid_search.py:224-320); its loss always shrinks coefficient 1."""
@@ -1150,20 +1179,10 @@ def nbinom_glm_gene(X, counts, size, offset, prior_no_shrink_scale, prior_scale,
         return nbinom_fn(beta, X, counts, size, offset, prior_no_shrink_scale, prior_scale, shrink_index) / cnst
 
     def df(beta):
-        xbeta = X @ beta
-        d_neg_prior = (beta * no_shrink_mask / prior_no_shrink_scale**2
-                       + 2 * beta * shrink_mask / (prior_scale**2 + beta[shrink_index] ** 2))
-        d_nll = (counts - (counts + size) / (1 + size * np.exp(-xbeta - offset))) @ X
-        return (d_neg_prior - d_nll) / cnst
+        return nbinom_grad(beta, X, counts, size, offset, prior_no_shrink_scale, prior_scale, shrink_index) / cnst
 
     def ddf(beta, c=1):
-        xbeta = X @ beta
-        e = np.exp(xbeta + offset)
-        frac = (counts + size) * size * e / (size + e) ** 2
-        h11 = 1 / prior_no_shrink_scale**2
-        h22 = 2 * (prior_scale**2 - beta[shrink_index] ** 2) / (prior_scale**2 + beta[shrink_index] ** 2) ** 2
-        h = np.diag(no_shrink_mask * h11 + shrink_mask * h22)
-        return 1 / c * ((X.T * frac) @ X + np.diag(h))
+        return 1 / c * nbinom_hess(beta, X, counts, size, offset, prior_no_shrink_scale, prior_scale, shrink_index)
 
     import warnings
 

@@ -1,8 +1,8 @@
 """ctypes front-end of the TEST-ONLY device build of dsq_math.h / dsq_wave.h (see devunit.hip) and of dsq_wide.h /
 dsq_wider.h / row_chol_solve (see devunit_linalg.hip), of dsq_stats.h / dsq_lds_sort.h (see devunit_stats.hip) and of
 dsq_lbfgsb_wave.h / dsq_lbfgsb.h / dsq_lbfgsb_par.h (see devunit_optim.hip), and of dsq_alpha.h's objective and the row
-kernels of the dispersion fit (see devunit_alpha.hip), and of the trend fit's passes and the product's trend unit (see
-devunit_trend.hip).
+kernels of the dispersion fit (see devunit_alpha.hip), of the trend fit's passes and the product's trend unit (see
+devunit_trend.hip), and of dsq_shrink.h's objective (see devunit_shrink.hip).
 
 Every function takes numpy arrays, pads them to whole 256-thread blocks where the caller has not, runs one entry point
 (allocate, copy, launch, synchronise, free) and raises on a non-zero hipError_t."""
@@ -681,3 +681,57 @@ def trend_loss_grad(cov, targets, a0, a1, keep=None):
     cnt = s[3]
     with np.errstate(all="ignore"):
         return np.float64(s[0]) / cnt, -np.float64(s[1]) / cnt, -np.float64(s[2]) / cnt, cnt
+
+
+# ------------------------------------------------------------------------------- dsq_shrink.h
+SHRINK_WIDE_INST = ((16, 16), (32, 24), (32, 32), (48, 40), (48, 48))  # (PMAX, PB) as launch_shrink picks them
+
+
+def shrink_rows(p, inst=None):
+    """rows of Xt and entries of b / g per gene: p for shrink_fn<P>, PB for shrink_fn_wide<PMAX, PB>"""
+    return p if inst is None else inst[1]
+
+
+def shrink_pack(y, offset, X, b, inst=None):
+    """The buffers of one shrink_fn call.  y / offset: [G][N], X: [G][N][p], b: [G][p] -> (y int32 [G][N], offset [G][N],
+    Xt [G][rows][N], b [G][rows], g [G][lanes][rows] is the caller's): rows and entries at index >= p hold NaN, so a read
+    beyond p poisons the result and never leaves the buffers."""
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    off, X, b = _d(offset), _d(X), _d(b)
+    G, N = y.shape
+    p = X.shape[2]
+    rows = shrink_rows(p, inst)
+    if off.shape != (G, N) or X.shape != (G, N, p) or b.shape != (G, p) or rows < p:
+        raise ValueError("y / offset must be [G][N], X [G][N][p], b [G][p], p <= PB")
+    Xt = np.full((G, rows, N), np.nan)
+    Xt[:, :p] = X.transpose(0, 2, 1)
+    bp = np.full((G, rows), np.nan)
+    bp[:, :p] = b
+    return y, off, np.ascontiguousarray(Xt), bp
+
+
+def shrink_fn(y, offset, X, size, sigma0, sigma, sidx, b, inst=None):
+    """shrink_fn<DeviceWave, p> (inst None, p <= 12: four genes per 256-thread block) or shrink_fn_wide<DeviceWave, *inst>
+    at the run-time p (one gene per 64-thread block), every gene with its own rows (shrink_pack).  Returns (f0 [G][64]:
+    the loss-only call, f1 [G][64]: the call with a gradient, g [G][64][rows]): what every lane holds; g is NaN before
+    the call."""
+    y, off, Xt, bp = shrink_pack(y, offset, X, b, inst)
+    G, N = y.shape
+    p, rows = X.shape[2], Xt.shape[1]
+    sz, s0, s = (_d(np.broadcast_to(v, (G,))) for v in (size, sigma0, sigma))
+    si = np.ascontiguousarray(np.broadcast_to(sidx, (G,)), dtype=np.int32)
+    f0, f1, g = np.full((G, 64), np.nan), np.full((G, 64), np.nan), np.full((G, 64, rows), np.nan)
+    pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    tail = [pi, pd, pd, C.c_int, C.c_int, C.c_int, pd, pd, pd, pi, pd, pd, pd, pd]
+    args = (_p(y, C.c_int32), _p(off, C.c_double), _p(Xt, C.c_double), N, N, G, _p(sz, C.c_double), _p(s0, C.c_double),
+            _p(s, C.c_double), _p(si, C.c_int32), _p(bp, C.c_double), _p(f0, C.c_double), _p(f1, C.c_double),
+            _p(g, C.c_double))
+    if inst is None:
+        fn = lib().du_shrink_fn
+        fn.argtypes, fn.restype = [C.c_int] + tail, C.c_int
+        _check(fn(p, *args), f"du_shrink_fn(P={p}, N={N}, G={G})")
+    else:
+        fn = lib().du_shrink_fn_wide
+        fn.argtypes, fn.restype = [C.c_int] * 3 + tail, C.c_int
+        _check(fn(inst[0], inst[1], p, *args), f"du_shrink_fn_wide({inst}, p={p}, N={N}, G={G})")
+    return f0, f1, g

@@ -14,6 +14,7 @@ SRC_STATS = os.path.join(HERE, "devunit_stats.hip")  # dsq_stats.h, dsq_lds_sort
 SRC_OPTIM = os.path.join(HERE, "devunit_optim.hip")  # dsq_lbfgsb_wave.h, dsq_lbfgsb.h, dsq_lbfgsb_par.h
 SRC_ALPHA = os.path.join(HERE, "devunit_alpha.hip")  # dsq_alpha.h; launches the two row-kernel units below
 SRC_TREND = os.path.join(HERE, "devunit_trend.hip")  # dsq_trend_grid.h; launches the trend unit below
+SRC_SHRINK = os.path.join(HERE, "devunit_shrink.hip")  # dsq_shrink.h: shrink_fn, shrink_fn_wide
 INC = os.path.join(ROOT, "pydeseq2_amd", "csrc")
 # the product's row kernels of the dispersion fit, unchanged and with the product's flags: devunit_alpha.hip calls their
 # launch_* entry points (dsq_launch.h)
@@ -21,7 +22,7 @@ SRC_ROWS = os.path.join(INC, "dsq_k_alpha_rows.hip")
 SRC_ROWSC = os.path.join(INC, "dsq_k_alpha_rowsc.hip")
 # the product's trend kernels and their launchers, likewise: devunit_trend.hip calls launch_trend_fit / _glm / _loss_grad
 SRC_KTREND = os.path.join(INC, "dsq_k_trend.hip")
-SRCS = [SRC, SRC_LINALG, SRC_STATS, SRC_OPTIM, SRC_ALPHA, SRC_TREND, SRC_ROWS, SRC_ROWSC, SRC_KTREND]
+SRCS = [SRC, SRC_LINALG, SRC_STATS, SRC_OPTIM, SRC_ALPHA, SRC_TREND, SRC_SHRINK, SRC_ROWS, SRC_ROWSC, SRC_KTREND]
 HOST_H = os.path.join(HERE, "devunit_host.h")
 OUT = os.path.join(HERE, "_devunit.so")
 MAKEFILE = os.path.join(INC, "Makefile")
@@ -58,7 +59,7 @@ def asm_cmd(out):
     """Device assembly of the library: shows which branches of the headers the device build took.  One output file
     takes one input, so the other units are read in front of the first (-include); their names do not collide."""
     return [HIPCC, *cxxflags(), "--cuda-device-only", "-S", "-I", INC, "--include=" + SRC_LINALG, "--include=" + SRC_STATS,
-            "--include=" + SRC_OPTIM, "--include=" + SRC_ALPHA, SRC, "-o", out]
+            "--include=" + SRC_OPTIM, "--include=" + SRC_ALPHA, "--include=" + SRC_SHRINK, SRC, "-o", out]
 
 
 def build(force=False):

@@ -440,6 +440,11 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "shrink_wider":  # round 6: apeGLM shrinkage for designs of 33 ... 48 columns
         shrink_wide_cases(ut, (("p40", 2), ("p48", 5)), "kat_shrink_wider.npz", 16)
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "shrink_rest":
+        # the register widths and shrink indices the other files leave out: k_shrink<1> and k_shrink<3> (no fixture
+        # before), and the first / last column as the shrunken coefficient -> kat_shrink_rest.npz (results only)
+        shrink_wide_cases(ut, (("p1", 0), ("p3", 2), ("p2", 0), ("p8", 7), ("p12", 11)), "kat_shrink_rest.npz", 24)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "shrink_wide":  # round 3: apeGLM shrinkage for designs of 13 ... 32 columns
         shrink_wide_cases(ut)
         return

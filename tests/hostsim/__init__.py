@@ -578,3 +578,26 @@ class PluginPool:
         out = (C.c_longlong * 10)()
         self.l.hs_pc_state(out)
         return dict(zip(self.STATE_FIELDS, list(out)))
+
+
+def shrink_fn(y, offset, X, size, sigma0, sigma, sidx, b, inst=None):
+    """shrink_fn<HostWave, p> (inst None) or shrink_fn_wide<HostWave, *inst> at the run-time p, every gene with its own
+    rows, buffers as tests/devunit packs them (NaN beyond p).  Returns (f0 [G]: the loss-only call, f1 [G], g [G][rows],
+    NaN before the call)."""
+    from tests.devunit import shrink_pack
+
+    y, off, Xt, bp = shrink_pack(y, offset, X, b, inst)
+    G, N = y.shape
+    p, rows = np.asarray(X).shape[2], Xt.shape[1]
+    sz, s0, s = (np.ascontiguousarray(np.broadcast_to(v, (G,)), dtype=np.float64) for v in (size, sigma0, sigma))
+    si = np.ascontiguousarray(np.broadcast_to(sidx, (G,)), dtype=np.int32)
+    f0, f1, g = np.full(G, np.nan), np.full(G, np.nan), np.full((G, rows), np.nan)
+    pd, pi = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    fn = lib().hs_shrink_fn
+    fn.argtypes = [C.c_int] * 3 + [pi, pd, pd, C.c_int, C.c_int, C.c_int, pd, pd, pd, pi, pd, pd, pd, pd]
+    fn.restype = C.c_int
+    rc = fn(0 if inst is None else inst[0], 0 if inst is None else inst[1], p, _p(y, C.c_int32), _p(off, C.c_double),
+            _p(Xt, C.c_double), N, N, G, _p(sz, C.c_double), _p(s0, C.c_double), _p(s, C.c_double), _p(si, C.c_int32),
+            _p(bp, C.c_double), _p(f0, C.c_double), _p(f1, C.c_double), _p(g, C.c_double))
+    assert rc == 0
+    return f0, f1, g

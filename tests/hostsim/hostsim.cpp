@@ -386,6 +386,43 @@ int hs_shrink(const int32_t* y, int ldn, const double* offset, const double* Xt,
     return 0;
 }
 
+// The apeGLM objective at caller-given coefficients, as tests/devunit/devunit_shrink.hip evaluates it on the device: every
+// gene has its own rows.  pmax == 0: shrink_fn<HostWave, p> (rows = p); else shrink_fn_wide<HostWave, pmax, pb> at the
+// run-time p (rows = pb).  y / offset: [G][ldx], Xt: [G][rows][ldx], b: [G][rows] -> f0 (loss-only call), f1, g: [G][rows]
+// (g keeps the caller's values where the template does not write)
+int hs_shrink_fn(int pmax, int pb, int p, const int32_t* y, const double* offset, const double* Xt, int ldx, int N, int G,
+                 const double* size, const double* sigma0, const double* sigma, const int32_t* sidx, const double* b,
+                 double* f0, double* f1, double* g) {
+    const int rows = pmax == 0 ? p : pb;
+    if (p < 1 || p > rows || N < 1 || ldx < N) return -1;
+    for (int k = 0; k < G; ++k) {
+        if (sidx[k] < 0 || sidx[k] >= p) return -1;
+        ShrinkArgs A;
+        A.y = y + (size_t)k * ldx; A.offset = offset + (size_t)k * ldx; A.Xt = Xt + (size_t)k * rows * ldx;
+        A.ldx = ldx; A.N = N;
+        A.size = size[k]; A.sigma0 = sigma0[k]; A.sigma = sigma[k]; A.shrink_index = sidx[k];
+        const double* xb = b + (size_t)k * rows;
+        double* gk = g + (size_t)k * rows;
+        bool found = false;
+        if (pmax == 0) {
+            if (p > DSQ_REG_MAX_P) return -1;
+            DSQ_DISPATCH_P(p, double bb[P]; for (int j = 0; j < P; ++j) bb[j] = xb[j];
+                           f0[k] = shrink_fn<HostWave, P>(A, bb, nullptr); f1[k] = shrink_fn<HostWave, P>(A, bb, gk);
+                           found = true)
+        }
+#define HS_WIDE(M_, B_)                                                        \
+    if (!found && pmax == M_ && pb == B_) {                                    \
+        f0[k] = shrink_fn_wide<HostWave, M_, B_>(A, p, xb, nullptr);           \
+        f1[k] = shrink_fn_wide<HostWave, M_, B_>(A, p, xb, gk);                \
+        found = true;                                                          \
+    }
+        HS_WIDE(16, 16) HS_WIDE(32, 24) HS_WIDE(32, 32) HS_WIDE(48, 40) HS_WIDE(48, 48)
+#undef HS_WIDE
+        if (!found) return -1;
+    }
+    return 0;
+}
+
 int hs_logmeans(const int32_t* y, int ldn, int N, int G, double* logmeans, uint8_t* nonzero) {
     for (int g = 0; g < G; ++g) {
         int nz;

@@ -47,12 +47,12 @@ def test_sources_are_the_test_units_and_the_product_units_they_launch():
     rel = [os.path.relpath(p, dub.ROOT) for p in dub.SRCS]
     assert rel == ["tests/devunit/devunit.hip", "tests/devunit/devunit_linalg.hip", "tests/devunit/devunit_stats.hip",
                    "tests/devunit/devunit_optim.hip", "tests/devunit/devunit_alpha.hip", "tests/devunit/devunit_trend.hip",
-                   "pydeseq2_amd/csrc/dsq_k_alpha_rows.hip", "pydeseq2_amd/csrc/dsq_k_alpha_rowsc.hip",
+                   "tests/devunit/devunit_shrink.hip", "pydeseq2_amd/csrc/dsq_k_alpha_rows.hip", "pydeseq2_amd/csrc/dsq_k_alpha_rowsc.hip",
                    "pydeseq2_amd/csrc/dsq_k_trend.hip"]
     assert all(os.path.exists(p) for p in dub.SRCS)
     cmd, asm = dub.compile_cmd(), dub.asm_cmd("x.s")
     assert all(p in cmd for p in dub.SRCS)
-    assert "--include=" + dub.SRC_ALPHA in asm
+    assert "--include=" + dub.SRC_ALPHA in asm and "--include=" + dub.SRC_SHRINK in asm
     assert not any("dsq_k_alpha_rows" in c or "dsq_k_trend" in c for c in asm)
     # the product builds the trend unit too (a unit of its own, so that it links here without the rest of dsq_k_stats.hip)
     assert "dsq_k_trend.hip" in dub.makefile_var("SRCS").split()

@@ -126,6 +126,28 @@ def test_lfc_shrink_inference_vs_reference_kats_at_the_widths_between(case):
         assert np.max(np.abs(ih - k[f"{case}{tag}_invh"]) / scale) < 1e-6
 
 
+@pytest.mark.parametrize("case", ["p1", "p3", "p2", "p8", "p12"])
+def test_lfc_shrink_inference_vs_reference_kats_at_the_other_widths_and_indices(case):
+    """k_shrink<1> and k_shrink<3>, which no other file fits, and the first / last column as the shrunken coefficient at
+    p = 2, 8, 12, against outputs of the unmodified utils.nbinomGLM (kat_shrink_rest.npz)."""
+    import os
+
+    from pydeseq2_amd import HipInference
+    from tests.helpers import load_kat
+
+    inf = HipInference(device=0)
+    k = np.load(os.path.join(os.path.dirname(__file__), "golden", "kat_shrink_rest.npz"))
+    kk = load_kat(case)
+    G, sidx = int(k[f"{case}_G"]), int(k[f"{case}_sidx"])
+    for tag in "ab":
+        b, ih, cv = inf.lfc_shrink_nbinom_glm(kk["X"], kk["counts"][:, :G], k[f"{case}_size"], np.log(kk["sf"]), 15,
+                                              float(k[f"{case}{tag}_scale"]), "L-BFGS-B", sidx)
+        assert (cv == k[f"{case}{tag}_conv"]).all()
+        np.testing.assert_allclose(b, k[f"{case}{tag}_beta"], rtol=1e-5, atol=1e-8)
+        scale = np.abs(k[f"{case}{tag}_invh"]).max(axis=(1, 2), keepdims=True)
+        assert np.max(np.abs(ih - k[f"{case}{tag}_invh"]) / scale) < 1e-6
+
+
 @pytest.mark.parametrize("case", ["p2", "p4", "p8", "p12"])
 @pytest.mark.parametrize("optimizer,tag", [("BFGS", "bfgs"), ("Newton-CG", "ncg")])
 def test_lfc_shrink_other_optimizers_vs_reference_kats(case, optimizer, tag):

@@ -497,6 +497,23 @@ def test_apeglm_shrinkage_templates_match_reference_at_the_widths_between(case):
         assert np.max(np.abs(ih - k[f"{case}{tag}_invh"]) / scale) < 1e-8
 
 
+@pytest.mark.parametrize("case", ["p1", "p3", "p2", "p8", "p12"])
+def test_apeglm_shrinkage_templates_match_reference_at_the_other_widths_and_indices(case):
+    """The two register widths no other file fits (p = 1 with the intercept shrunk, p = 3 with its last column) and the
+    first / last column as the shrunken coefficient at p = 2, 8, 12 (kat_shrink_rest.npz, the unmodified utils.nbinomGLM)."""
+    k = np.load(os.path.join(os.path.dirname(__file__), "golden", "kat_shrink_rest.npz"))
+    kk = load_kat(case)
+    G, sidx = int(k[f"{case}_G"]), int(k[f"{case}_sidx"])
+    assert sidx == {"p1": 0, "p3": 2, "p2": 0, "p8": 7, "p12": 11}[case]
+    for tag in "ab":
+        b, ih, cv = hs.shrink(kk["counts"][:, :G], kk["X"], k[f"{case}_size"], np.log(kk["sf"]), 15.0,
+                              float(k[f"{case}{tag}_scale"]), sidx)
+        assert (cv == k[f"{case}{tag}_conv"]).all()
+        np.testing.assert_allclose(b, k[f"{case}{tag}_beta"], rtol=1e-6, atol=1e-9)
+        scale = np.abs(k[f"{case}{tag}_invh"]).max(axis=(1, 2), keepdims=True)
+        assert np.max(np.abs(ih - k[f"{case}{tag}_invh"]) / scale) < 1e-8
+
+
 @pytest.mark.parametrize("case", ["p2", "p4", "p8", "p12"])
 @pytest.mark.parametrize("optimizer,tag", [("BFGS", "bfgs"), ("Newton-CG", "ncg")])
 def test_apeglm_shrinkage_other_optimizers_match_reference(case, optimizer, tag):
