@@ -517,6 +517,31 @@ int dsq_dev_rlog(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, 
 int dsq_dev_ash(dsq_ctx* ctx, const double* d_lfc, const double* d_se, int G, int ldg, int K, const double* d_sd,
                 const int32_t* d_m, int ldm, int max_iter, double* d_pi, double* d_post_mean, double* d_post_sd,
                 double* d_lfsr, int32_t* d_niter, uint8_t* d_conv, double* d_kkt, double* d_loglik);
+/* Wilcoxon rank-sum test (Mann-Whitney; with strata: van Elteren) of K comparisons on the normalised counts
+ * v = (double)y / sf (IEEE division) of the gene-major int32 rows d_y (pitch ldn); csrc/dsq_rank.h, DESIGN.md 6k.  One gene
+ * per wavefront, grid.y = the comparison; no atomics: the same call gives the same bits, and K comparisons the bits of K
+ * calls.  Comparison k (rows of pitch ldo / lds / ldl): d_nstrata[k] = S strata; d_order[k][d_seg[k][s] .. d_seg[k][s+1]):
+ * the indices of the used samples of stratum s; d_pad[k][s]: prefix sums of next_pow2(N_s), the stratum's place in the
+ * gene's LDS row, d_pad[k][S] = L doubles; d_labels[k][n] int8: 1 tested, 0 reference (anything else, or a sample that is
+ * not in d_order: left out).  Per stratum with both groups: U_s = R_s - n1 (n1 + 1) / 2 from the tested samples' midranks,
+ * T_s = sum over tie runs of t^3 - t; W = sum_s w_s (U_s - n1 n2 / 2), V = sum_s w_s^2 n1 n2 ((N_s^3 - N_s) - T_s) /
+ * (12 N_s (N_s - 1)), w_s = 1 and continuity correction c = 0.5 for S == 1, w_s = 1 / (N_s + 1) and c = 0 otherwise.
+ * alt (dsq_alt) 0: stat = sign(W) max(|W| - c, 0) / sqrt V, p = min(1, 2 sf(|stat|)); 3 "greater": stat = (W - c) / sqrt V,
+ * p = sf(stat); 4 "less": stat = (W + c) / sqrt V, p = sf(-stat); V == 0: stat 0, p 1.  Outputs [K][ldg]: d_stat, d_pvalue,
+ * d_usum = sum_s U_s (an exact half-integer), d_ties = sum_s T_s (an exact integer).  For S == 1 this is
+ * scipy.stats.mannwhitneyu(tested, reference, use_continuity=True, method="asymptotic").
+ * dsq_ranksum_plan: the launch plan of a padded row of L doubles - wavefronts (genes) per workgroup and its dynamic LDS
+ * bytes: 4 up to 5120 doubles, 2 up to 10 240, 1 up to DSQ_RANK_MAX_L (128 KiB); DSQ_ERR_ARG (and 0, 0) outside 1 ... 16 384.
+ * DSQ_ERR_ARG: N < 2, G < 0, K outside 1 ... 65 535, a pitch below its row, an alt other than 0 / 3 / 4, a null pointer, a
+ * layout that is not as described (S outside 1 ... lds - 1, an empty stratum, offsets that do not start at 0, pads that are
+ * not the prefix sums, a sample index outside 0 ... N - 1) or L > DSQ_RANK_MAX_L.  The layouts are read back and checked on
+ * the host before the launch.  G == 0 does nothing. */
+#define DSQ_RANK_MAX_L 16384 /* LDS doubles per gene of dsq_dev_ranksum: the sum over the strata of next_pow2(N_s) */
+int dsq_ranksum_plan(int L, int* waves, size_t* lds_bytes);
+int dsq_dev_ranksum(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, int N, int G, int K,
+                    const int32_t* d_order, int ldo, const int32_t* d_seg, const int32_t* d_pad, int lds,
+                    const int32_t* d_nstrata, const int8_t* d_labels, int ldl, int alt, double* d_stat, double* d_pvalue,
+                    double* d_usum, double* d_ties, int ldg);
 /* Sample PCA and sample distances of a transformed matrix (DESeq2's plotPCA and dist on vst / rlog values; csrc/dsq_gram.h,
  * DESIGN.md 6j).  d_x: N samples x G genes of finite doubles in `layout` (dsq_layout): DSQ_SAMPLE_MAJOR [N][ld], ld >= G, or
  * DSQ_GENE_MAJOR [G][ld], ld >= N; what lies in the row padding is never read.  All index arithmetic in 64 bits.

@@ -213,6 +213,9 @@ def load():
     proto("dsq_dev_chisq_sf", _vp, _vp, c_int, c_int, _vp)
     proto("dsq_dev_rlog", _vp, _vp, c_int, _vp, c_int, c_int, _vp, _vp, c_double, _vp, _vp, _vp, _vp)
     proto("dsq_dev_ash", _vp, _vp, _vp, c_int, c_int, c_int, _vp, _vp, c_int, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
+    proto("dsq_ranksum_plan", c_int, C.POINTER(c_int), C.POINTER(c_size_t))
+    proto("dsq_dev_ranksum", _vp, _vp, c_int, _vp, c_int, c_int, c_int, _vp, c_int, _vp, _vp, c_int, _vp, _vp, c_int, c_int,
+          _vp, _vp, _vp, _vp, c_int)
     proto("dsq_dev_row_meanvar", _vp, _vp, c_int, c_int, c_int, c_int, _vp, _vp)
     proto("dsq_sample_gram_work_doubles", c_int, c_int, res=c_size_t)
     proto("dsq_dev_sample_gram", _vp, _vp, c_int, c_int, c_int, c_int, _vp, c_int, _vp, _vp, _vp, c_int)
@@ -256,6 +259,7 @@ EXPORTS = [
     "dsq_lfc_fork_begin", "dsq_lfc_fork_end", "dsq_lfc_set_part", "dsq_lfc_takes_parts", "dsq_dev_select_dispersions_part", "dsq_lfc_prepare", "dsq_alpha_set_late_flags",
     "dsq_dev_lrt", "dsq_dev_chisq_sf", "dsq_dev_wald_multi", "dsq_dev_rlog", "dsq_dev_ash",
     "dsq_dev_row_meanvar", "dsq_sample_gram_work_doubles", "dsq_dev_sample_gram", "dsq_dev_gram_dist",
+    "dsq_ranksum_plan", "dsq_dev_ranksum",
 ]
 
 

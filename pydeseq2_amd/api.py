@@ -17,6 +17,7 @@ import warnings
 import numpy as np
 import pandas as pd
 
+from . import ranktest as _ranktest
 from . import summary as _summary
 from ._design import DesignPack
 from . import _lib
@@ -939,14 +940,35 @@ class DeseqStats:
     ``test="LRT"`` with ``reduced=`` (a formula over the same metadata such as ``"~batch"`` or ``"~1"``, a matrix or a
     DataFrame whose columns span a subspace of the full design's) replaces the Wald statistic and p-value by those of
     the likelihood-ratio test of the reduced design (DESeq2's ``nbinomLRT``); ``log2FoldChange`` / ``lfcSE`` stay those
-    of the contrast, and the p-values pass through the same Cook's filter, independent filtering and BH."""
+    of the contrast, and the p-values pass through the same Cook's filter, independent filtering and BH.
+
+    ``test="wilcoxon"`` replaces them by the Wilcoxon rank-sum test (Mann-Whitney, normal approximation with tie and
+    continuity correction) of the tested against the reference level of a ``[factor, tested, ref]``
+    contrast on the normalised counts - the distribution-free cross-check of a large cohort.  ``strata=`` (an ``obs``
+    column or a list of them, their levels crossed) makes it van Elteren's stratified test.  ``alt_hypothesis``: None,
+    "greater" or "less".  ``summary()`` keeps ``baseMean``, ``log2FoldChange`` and ``lfcSE`` of the GLM fit, passes the rank
+    test's p-values through independent filtering and BH and adds ``auc``; the Cook's filter is NOT applied: an outlying
+    count moves a rank by at most one group size, which is what the test is robust against.  Single process only, like
+    ``test="LRT"``: the distributed pipeline has no rank-sum launch."""
 
     def __init__(self, dds: DeseqDataSet, contrast, alpha=0.05, cooks_filter=True, independent_filter=True,
                  prior_LFC_var=None, lfc_null=0.0, alt_hypothesis=None, inference=None, quiet=True, n_cpus=None, *,
-                 test="wald", reduced=None):
-        if test not in ("wald", "LRT"):
-            raise ValueError(f"test must be 'wald' or 'LRT' (got {test!r}).")
-        self.test, self.reduced_design = test, None
+                 test="wald", reduced=None, strata=None):
+        if test not in ("wald", "LRT", "wilcoxon"):
+            raise ValueError(f"test must be 'wald' or 'LRT', or 'wilcoxon' for the rank-sum test (got {test!r}).")
+        self.test, self.reduced_design, self.strata = test, None, None
+        if test == "wilcoxon":  # (host-only checks: before anything touches the GPU)
+            _ranktest.check_alternative(alt_hypothesis, lfc_null)
+            if contrast is not None and (isinstance(contrast, np.ndarray) or not isinstance(contrast[0], str)):
+                raise ValueError("test='wilcoxon' compares the samples of two levels of a factor: the contrast must be "
+                                 "[factor, tested, ref] (a numeric contrast vector names no two groups of samples).")
+            if strata is not None:
+                self.strata = [strata] if isinstance(strata, str) else [str(c) for c in strata]
+                missing = [c for c in self.strata if c not in dds.obs.columns]
+                if missing or not self.strata:
+                    raise ValueError(f"strata must name columns of the metadata (not found: {missing}).")
+        elif strata is not None:
+            raise ValueError("strata are the strata of the rank-sum test: pass test='wilcoxon' with them.")
         if test == "LRT":  # (host-only checks: before anything touches the GPU)
             if reduced is None:
                 raise ValueError("test='LRT' needs a reduced design: reduced='~batch', '~1', a matrix or a DataFrame.")
@@ -971,6 +993,26 @@ class DeseqStats:
         self.contrast = contrast
         self.contrast_vector = self._contrast_vector(contrast)
         self.shrunk_LFCs = False
+        if test == "wilcoxon":
+            self._rank_layout()
+
+    def _rank_layout(self):
+        """Labels (1 tested, 0 reference, -1 left out) and stratum ids of the rank-sum test, from ``obs``: host only."""
+        factor, tested, ref = (str(c) for c in self.contrast[:3])
+        if tested == ref:
+            raise ValueError(f"test='wilcoxon': the tested and the reference level are the same ('{tested}').")
+        lv = self.dds.obs[factor].astype(str).to_numpy()
+        self._rank_labels = np.where(lv == tested, 1, np.where(lv == ref, 0, -1)).astype(np.int8)
+        self._rank_strata = None
+        if self.strata is not None:
+            key = self.dds.obs[self.strata].astype(str).agg("\x1f".join, axis=1)
+            self._rank_strata = pd.factorize(key, sort=True)[0].astype(np.int64)
+        _ranktest.build_layout(self._rank_labels, self._rank_strata)  # (refuses rows that do not fit the LDS)
+        n1, n2 = int((self._rank_labels == 1).sum()), int((self._rank_labels == 0).sum())
+        if min(n1, n2) < 8:
+            warnings.warn(f"test='wilcoxon': {n1} tested and {n2} reference samples - below 8 per group the normal "
+                          "approximation of the rank-sum statistic is poor and small p-values are out of reach.",
+                          UserWarning, stacklevel=3)
 
     def _contrast_vector(self, contrast) -> np.ndarray:
         # errors as in the reference (ds.py:172-188, tests/test_edge_cases.py::test_contrast): IndexError for a
@@ -1013,9 +1055,11 @@ class DeseqStats:
         ``statistics`` and ``SE`` filled, so ``summary()`` goes straight to the filters and BH; ``summary(lfc_null=...)``
         with other values, ``lfc_shrink`` etc. behave as on any other ``DeseqStats`` (the single-contrast path).
         A bad contrast raises what ``DeseqStats(...)`` raises for it, before anything is launched.  The likelihood-ratio
-        statistic does not depend on the contrast: ``test="LRT"`` is refused.  Single process only: the distributed
-        pipeline has no multi-contrast launch."""
-        if kwargs.get("test", "wald") != "wald" or kwargs.get("reduced") is not None:
+        statistic does not depend on the contrast: ``test="LRT"`` is refused.  ``test="wilcoxon"`` (with ``strata=``,
+        ``alt_hypothesis``): every contrast a ``[factor, tested, ref]`` list; the rank-sum tests of all of them run in
+        one launch (``DeseqPipeline.ranksum``) after the Wald launch that gives ``lfcSE``.  Single process only: the
+        distributed pipeline has no multi-contrast launch."""
+        if kwargs.get("test", "wald") not in ("wald", "wilcoxon") or kwargs.get("reduced") is not None:
             raise ValueError("DeseqStats.batch() runs Wald tests: the likelihood-ratio statistic does not depend on the "
                              "contrast (use DeseqStats(dds, contrast, test='LRT', reduced=...) once).")
         contrasts = list(contrasts)
@@ -1029,6 +1073,11 @@ class DeseqStats:
         for k, o in enumerate(out):
             o.p_values, o.statistics, o.SE = (pd.Series(v[k], index=idx) for v in (pv, st, se))
             o._wald_key = (o.lfc_null, o.alt_hypothesis)
+        if first.test == "wilcoxon":  # (the Wald launch above gave lfcSE; the rank tests of all comparisons in one more)
+            r = dds._pipe.ranksum(dds._res, np.stack([o._rank_labels for o in out]), first._rank_strata,
+                                  first.alt_hypothesis)
+            for k, o in enumerate(out):
+                o._set_ranksum(r, k)
         return out
 
     def run_wald_test(self):
@@ -1060,21 +1109,50 @@ class DeseqStats:
         if hasattr(self, "padj"):
             del self.padj
 
+    def run_ranksum_test(self):
+        """Wilcoxon rank-sum test of the contrast's two levels (``DeseqPipeline.ranksum``): ``statistics`` (the z
+        statistic), ``p_values`` and ``auc`` (the probability that a tested sample lies above a reference sample of its
+        stratum, ties counting half) are the rank test's, also ``rank_usum`` and ``rank_ties``; ``SE`` stays the contrast's
+        standard error (a Wald quantity)."""
+        if self.test != "wilcoxon":
+            raise ValueError("run_ranksum_test() needs DeseqStats(..., test='wilcoxon').")
+        _ranktest.check_alternative(self.alt_hypothesis, self.lfc_null)
+        if not hasattr(self, "SE"):
+            self.run_wald_test()
+        r = self.dds._pipe.ranksum(self.dds._res, self._rank_labels, self._rank_strata, self.alt_hypothesis)
+        self._set_ranksum(r, 0)
+
+    def _set_ranksum(self, r, k):
+        idx = self.dds.var_names
+        self.p_values, self.statistics = pd.Series(r.pvalue[k], index=idx), pd.Series(r.statistic[k], index=idx)
+        self.auc = pd.Series(r.auc[k], index=idx)
+        self.rank_usum, self.rank_ties = pd.Series(r.usum[k], index=idx), pd.Series(r.ties[k], index=idx)
+        self._wald_key = ("wilcoxon", self.alt_hypothesis)
+        if hasattr(self, "padj"):
+            del self.padj
+
     def summary(self, **kwargs) -> pd.DataFrame:
         """Wald test, Cook's filtering, adjusted p-values; returns and stores ``results_df`` (ds.py:219-299).
         The Wald test is (re)run only when there are no p-values yet or ``lfc_null`` / ``alt_hypothesis`` change
         (ds.py:255-264), so a summary after ``lfc_shrink`` keeps the shrunk coefficients with their standard errors.
-        With ``test="LRT"`` the statistic and the p-values are the likelihood-ratio test's."""
+        With ``test="LRT"`` the statistic and the p-values are the likelihood-ratio test's; with ``test="wilcoxon"``
+        the rank-sum test's, without the Cook's filter (the test is rank-based) and with an ``auc`` column."""
+        if self.test == "wilcoxon":  # (refused before the object changes)
+            _ranktest.check_alternative(kwargs.get("alt_hypothesis", self.alt_hypothesis),
+                                        kwargs.get("lfc_null", self.lfc_null))
         self.lfc_null = kwargs.get("lfc_null", self.lfc_null)
         self.alt_hypothesis = kwargs.get("alt_hypothesis", self.alt_hypothesis)
         if self.test == "LRT":
             _check_lrt_hypothesis(self.lfc_null, self.alt_hypothesis)
             if getattr(self, "_wald_key", None) != ("LRT",):
                 self.run_lrt_test()
+        elif self.test == "wilcoxon":
+            if getattr(self, "_wald_key", None) != ("wilcoxon", self.alt_hypothesis):
+                self.run_ranksum_test()
         elif not hasattr(self, "p_values") or getattr(self, "_wald_key", None) != (self.lfc_null, self.alt_hypothesis):
             self.run_wald_test()
         if not hasattr(self, "padj"):
-            if self.cooks_filter:
+            if self.cooks_filter and self.test != "wilcoxon":  # (rank-based: no Cook's filter, see the class)
                 self._cooks_filtering()
             if self.independent_filter:
                 self._independent_filtering()
@@ -1087,6 +1165,8 @@ class DeseqStats:
             df["log2FoldChange"] = self.ash_LFC / np.log(2)
         df["lfcSE"] = self.SE / np.log(2)
         df["stat"], df["pvalue"], df["padj"] = self.statistics, self.p_values, self.padj
+        if self.test == "wilcoxon":
+            df["auc"] = self.auc
         if getattr(self, "_ash_svalue", False):
             df["svalue"] = self.svalues
         self.results_df = df

@@ -1,5 +1,6 @@
 // dsq_capi_dev.hip — the stages of the path on device-resident buffers (dsq_dev_*, dsq_mix_*; include/deseq_hip.h).
 #include "dsq_capi_internal.h"
+#include "dsq_rank.h"
 
 extern "C" {
 
@@ -669,6 +670,50 @@ int dsq_dev_ash(dsq_ctx* ctx, const double* d_lfc, const double* d_se, int G, in
     DSQ_HIP(dsq::launch_ash_fit(ctx->stream, d_lfc, d_se, G, ldg, K, d_sd, d_m, ldm, max_m, max_iter, d_pi, d_niter, d_conv,
                                 d_kkt, d_loglik));
     DSQ_HIP(dsq::launch_ash_post(ctx->stream, d_lfc, d_se, G, ldg, K, d_sd, d_m, ldm, d_pi, d_post_mean, d_post_sd, d_lfsr));
+    return DSQ_OK;
+}
+
+int dsq_ranksum_plan(int L, int* waves, size_t* lds_bytes) {
+    const dsq::RankPlan p = dsq::rank_plan(L);
+    if (waves != nullptr) *waves = p.waves;
+    if (lds_bytes != nullptr) *lds_bytes = p.lds_bytes;
+    return p.waves > 0 ? DSQ_OK : DSQ_ERR_ARG;
+}
+
+int dsq_dev_ranksum(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, int N, int G, int K,
+                    const int32_t* d_order, int ldo, const int32_t* d_seg, const int32_t* d_pad, int lds,
+                    const int32_t* d_nstrata, const int8_t* d_labels, int ldl, int alt, double* d_stat, double* d_pvalue,
+                    double* d_usum, double* d_ties, int ldg) {
+    DSQ_CHECK_ARG(N >= 2, "N: at least two samples");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(K >= 1 && K <= 65535, "K: between 1 and 65535 comparisons");
+    DSQ_CHECK_ARG(ldn >= N && ldl >= N, "ldn or ldl is smaller than N");
+    DSQ_CHECK_ARG(ldo >= 1 && lds >= 2, "ldo: at least 1, lds: at least 2 (one stratum)");
+    DSQ_CHECK_ARG(ldg >= G, "ldg is smaller than G");
+    DSQ_CHECK_ARG(alt == 0 || alt == 3 || alt == 4, "alt: two-sided (0), greater (3) or less (4)");
+    DSQ_CHECK_ARG(d_order != nullptr && d_seg != nullptr && d_pad != nullptr && d_nstrata != nullptr && d_labels != nullptr,
+                  "a layout pointer is null");
+    DSQ_CHECK_ARG(d_stat != nullptr && d_pvalue != nullptr && d_usum != nullptr && d_ties != nullptr,
+                  "an output pointer is null");
+    // (the layouts decide the launch and index the LDS: back to the host, checked there - a few integers per sample)
+    std::vector<int32_t> ns((size_t)K), seg((size_t)K * lds), pad((size_t)K * lds), order((size_t)K * ldo);
+    DSQ_HIP(hipMemcpyAsync(ns.data(), d_nstrata, ns.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    DSQ_HIP(hipMemcpyAsync(seg.data(), d_seg, seg.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    DSQ_HIP(hipMemcpyAsync(pad.data(), d_pad, pad.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    DSQ_HIP(hipMemcpyAsync(order.data(), d_order, order.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    DSQ_HIP(hipStreamSynchronize(ctx->stream));
+    int L = 0;
+    for (int k = 0; k < K; ++k) {
+        const char* why = dsq::rank_check_layout(order.data() + (size_t)k * ldo, seg.data() + (size_t)k * lds,
+                                                 pad.data() + (size_t)k * lds, ns[k], lds - 1, ldo, N);
+        if (why != nullptr) return fail(ctx, DSQ_ERR_ARG, why);
+        const int Lk = pad[(size_t)k * lds + ns[k]];
+        L = Lk > L ? Lk : L;
+    }
+    if (G == 0) return DSQ_OK;
+    DSQ_CHECK_ARG(d_y != nullptr && d_sf != nullptr, "an input pointer is null");
+    DSQ_HIP(dsq::launch_ranksum(ctx->stream, d_y, ldn, d_sf, G, K, d_order, ldo, d_seg, d_pad, lds, d_nstrata, d_labels, ldl,
+                                alt, L, d_stat, d_pvalue, d_usum, d_ties, ldg));
     return DSQ_OK;
 }
 

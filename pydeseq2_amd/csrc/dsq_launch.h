@@ -338,6 +338,12 @@ hipError_t launch_ash_fit(hipStream_t st, const double* lfc, const double* se, i
                           double* kkt, double* loglik);
 hipError_t launch_ash_post(hipStream_t st, const double* lfc, const double* se, int G, int ldg, int K, const double* sd,
                            const int32_t* m, int ldm, const double* pi, double* post_mean, double* post_sd, double* lfsr);
+// ---- dsq_k_rank.hip: Wilcoxon rank-sum test of K comparisons (dsq_rank.h); L: the longest padded row, at most
+// kRankMaxL; the layouts have been checked by the caller (rank_check_layout); outputs [K][ldg]
+hipError_t launch_ranksum(hipStream_t st, const int32_t* y, int ldn, const double* sf, int G, int K, const int32_t* order,
+                          int ldo, const int32_t* seg, const int32_t* pad, int lds, const int32_t* nstrata,
+                          const int8_t* labels, int ldl, int alt, int L, double* stat, double* pvalue, double* usum,
+                          double* ties, int ldg);
 // ---- dsq_k_gram.hip: sample PCA / sample distances of a transformed matrix (dsq_gram.h): per-gene means and variances
 // (layout as dsq_layout, var may be null), the centred N x N Gram over a gene list (work: sample_gram_work_doubles) and
 // the Euclidean distances from it

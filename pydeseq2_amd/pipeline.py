@@ -1591,6 +1591,24 @@ class DeseqPipeline:
 
         return ash(self, lfc, se)
 
+    # ------------------------------------------------------------------ rank-sum test
+    def ranksum(self, res: DeseqResult, labels, strata=None, alt_hypothesis=None):
+        """Wilcoxon rank-sum test (with ``strata``: van Elteren's stratified test; csrc/dsq_rank.h) of K
+        comparisons, post hoc like wald() and lrt(), on the resident ORIGINAL counts (never the replaced ones: the test is
+        rank-based) normalised by the size factors of ``res``.  ``labels``: K x N (or one vector), 1 = tested level, 0 =
+        reference level, -1 = left out; ``strata``: one integer id per sample, or None; ``alt_hypothesis``: None,
+        "greater" or "less".  All comparisons run in one launch.  Returns a pydeseq2_amd.ranktest.RankSumResult; genes
+        without counts (``non_zero`` false) get NaN in every column.  (Single process: the gene-sharded pipeline has no
+        counterpart, as for lrt().)"""
+        from .ranktest import ranksum
+
+        out = ranksum(self, self.d_y.ptr, self.ldn, res.size_factors, self.G, labels, strata, alt_hypothesis)
+        z = ~np.asarray(res.non_zero, dtype=bool)
+        if z.any():
+            for a in (out.statistic, out.pvalue, out.usum, out.ties, out.auc):
+                a[:, z] = np.nan
+        return out
+
     def pca(self, x, ntop=500, n_components=None):
         """Sample PCA of a transformed N x G matrix (DESeq2's plotPCA; csrc/dsq_gram.h) on this pipeline's
         device: pydeseq2_amd.pca.pca.  (Single process: the gene-sharded pipeline has no counterpart.)"""
