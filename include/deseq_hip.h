@@ -567,6 +567,35 @@ size_t dsq_sample_gram_work_doubles(int N, int K);
 int dsq_dev_sample_gram(dsq_ctx* ctx, const double* d_x, int layout, int N, int G, int ld, const int32_t* d_sel, int K,
                         const double* d_mean, double* d_work, double* d_S, int lds);
 int dsq_dev_gram_dist(dsq_ctx* ctx, const double* d_S, int N, int lds, double* d_D, int ldd);
+/* Hidden-batch factors (RUVg, RUVr) and batch removal (limma's removeBatchEffect): the three per-gene operations of
+ * csrc/dsq_proj.h, one gene per wavefront, fp64, no atomics: the same call gives the same bits.
+ * dsq_dev_log_counts: d_out [G][ld] = log(v + eps) of the gene-major int32 rows d_y (pitch ldn), v = (double)y / sf_n by
+ *   IEEE division when `normalized`, v = y otherwise (d_sf may then be null).
+ * dsq_dev_nb_residuals: d_out [G][ld] = the residuals of the NB GLM from a finished fit: mu = sf_n exp(x_n . beta_g)
+ *   unthresholded (d_Xt: the transposed design [P][ldx], d_beta [G][P] natural log), r = 1 / d_disp[g].  kind 0, deviance:
+ *   sign(y - mu) sqrt(max(D, 0)), D = 2 [y log(y / mu) - (y + r) log((y + r) / (mu + r))] (y = 0: 2 r log1p(mu / r)), both
+ *   logarithms as +-log1p((hi - lo) / lo): exactly 0 where y == mu.  kind 1, Pearson: (y - mu) / sqrt(mu + disp mu^2).  A
+ *   gene whose counts are all zero, or with a NaN coefficient or dispersion: a row of NaN.
+ * dsq_dev_project_out: c_gj = sum_n x_gn P_nj, out_gn = x_gn - sum_j c_gj B_nj for the gene-major d_x [G][ld]; d_Pt and
+ *   d_Bt: the two N x q matrices transposed, [q][ldp].  post 0: nothing; 1: exp(out) - eps; 2: max(rint(exp(out) - eps), 0).
+ *   Lane l of the wavefront sums n = l, l + 64, ... ascending (fma), the lanes are added by the butterfly of distances 32,
+ *   16, 8, 4, 2, 1, the subtraction is a chain of fma(-c_j, B_nj, .) with j ascending.  d_out [G][ldo] may be d_x (with ldo
+ *   == ld); d_coef [G][q] or null.  What lies in the row padding is neither read nor written.
+ * dsq_project_plan: the launch plan of rows of N doubles - wavefronts (genes) per workgroup, where a wavefront keeps its
+ *   row between the passes (*staged = 2: in registers, up to N = 1024, 4 per workgroup; 1: in LDS, 4 per workgroup up to
+ *   N = 4800, 2 up to 9664, 1 up to 16 320; 0: nowhere - re-read from memory in every pass, 4 per workgroup), and the
+ *   workgroup's dynamic LDS bytes; DSQ_ERR_ARG (and zeros) for N < 1.
+ * DSQ_ERR_ARG: N < 1, G < 0, a pitch below N, eps not finite or not positive (log counts; post != 0), an unknown kind or
+ *   post, P outside 1 ... DSQ_MAX_P, q outside 1 ... DSQ_PROJ_MAX_Q, d_out == d_x with another pitch, a null pointer where
+ *   one is needed.  G == 0 does nothing. */
+#define DSQ_PROJ_MAX_Q 64 /* columns of P and B of dsq_dev_project_out */
+int dsq_dev_log_counts(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, int N, int G, int normalized,
+                       double eps, double* d_out, int ld);
+int dsq_dev_nb_residuals(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, const double* d_Xt, int ldx, int P,
+                         int N, int G, const double* d_disp, const double* d_beta, int kind, double* d_out, int ld);
+int dsq_project_plan(int N, int* waves, int* staged, size_t* lds_bytes);
+int dsq_dev_project_out(dsq_ctx* ctx, const double* d_x, int ld, const double* d_Pt, const double* d_Bt, int ldp, int q,
+                        int N, int G, int post, double eps, double* d_out, int ldo, double* d_coef);
 /* row gathers for the refit sub-problem: dst[k][:] = src[idx[k]][:] */
 /* O(G) glue that keeps the dispersion vectors device-resident between the stages:
  * fitted trend a0 + a1/normed_mean (dds.py:826-833; a1 == 0: mean trend), final dispersions with the

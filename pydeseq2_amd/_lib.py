@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("DSQ_LIB", os.path.join(_HERE, "libdeseq_hip.so"))  # 
 
 DSQ_MAX_P = 128
 DSQ_SHRINK_MAX_P = 48  # apeGLM shrinkage (dsq_*_lfc_shrink*)
+DSQ_PROJ_MAX_Q = 64  # columns of P and B of dsq_dev_project_out
 _DEBUG = bool(os.environ.get("DSQ_DEBUG"))
 SAMPLE_MAJOR, GENE_MAJOR = 0, 1
 I32, I64 = 0, 1
@@ -220,6 +221,10 @@ def load():
     proto("dsq_sample_gram_work_doubles", c_int, c_int, res=c_size_t)
     proto("dsq_dev_sample_gram", _vp, _vp, c_int, c_int, c_int, c_int, _vp, c_int, _vp, _vp, _vp, c_int)
     proto("dsq_dev_gram_dist", _vp, _vp, c_int, c_int, _vp, c_int)
+    proto("dsq_dev_log_counts", _vp, _vp, c_int, _vp, c_int, c_int, c_int, c_double, _vp, c_int)
+    proto("dsq_dev_nb_residuals", _vp, _vp, c_int, _vp, _vp, c_int, c_int, c_int, c_int, _vp, _vp, c_int, _vp, c_int)
+    proto("dsq_project_plan", c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_size_t))
+    proto("dsq_dev_project_out", _vp, _vp, c_int, _vp, _vp, c_int, c_int, c_int, c_int, c_int, c_double, _vp, c_int, _vp)
     proto("dsq_dev_gather_rows_f64", _vp, _vp, c_int, _vp, c_int, c_int, _vp)
     proto("dsq_dev_gather_rows_i32", _vp, _vp, c_int, _vp, c_int, c_int, _vp)
     proto("dsq_comm_unique_id", _vp, C.c_char_p, c_int)
@@ -260,6 +265,7 @@ EXPORTS = [
     "dsq_dev_lrt", "dsq_dev_chisq_sf", "dsq_dev_wald_multi", "dsq_dev_rlog", "dsq_dev_ash",
     "dsq_dev_row_meanvar", "dsq_sample_gram_work_doubles", "dsq_dev_sample_gram", "dsq_dev_gram_dist",
     "dsq_ranksum_plan", "dsq_dev_ranksum",
+    "dsq_dev_log_counts", "dsq_dev_nb_residuals", "dsq_project_plan", "dsq_dev_project_out",
 ]
 
 

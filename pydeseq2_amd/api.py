@@ -784,6 +784,91 @@ class DeseqDataSet:
         x = self._transformed_layer(layer, "sample_distances()")
         return pd.DataFrame(_pca.sample_distances(self._pipe, x), index=self.obs_names, columns=self.obs_names)
 
+    # ------------------------------------------------------------------ hidden batch
+    def _fitted(self, what):
+        if self._res is None or getattr(self._res, "LFC", None) is None:
+            raise ValueError(f"{what}: run deseq2() first (the fit's coefficients, dispersions and size factors are needed).")
+        return self._res
+
+    def residuals(self, type: str = "deviance"):
+        """Residuals of the fitted NB GLM, an N x G DataFrame (``type``: "deviance" or "pearson"): from the coefficients,
+        dispersions and size factors of the last ``deseq2()`` and the original counts.  Genes without counts: NaN."""
+        from . import ruv as _ruv
+
+        if type not in _ruv.KIND:
+            raise ValueError(f"type must be 'deviance' or 'pearson' (got {type!r}).")
+        r = self._fitted("residuals()")
+        return pd.DataFrame(self._pipe.residuals(r, type), index=self.obs_names, columns=self.var_names)
+
+    def ruv(self, k, control_genes=None, method="g", normalized=True, epsilon=1.0, center=True, drop=0, counts=False,
+            round=True, corrected=False):
+        """Factors of unwanted variation (RUVSeq's ``RUVg`` / ``RUVr``): k factors from the control genes of the log
+        normalised counts (``method="g"``: ``control_genes`` - names, positions or a mask - is required, e.g.
+        ``DeseqStats.empirical_controls()``) or of the deviance residuals of the fit (``"r"``, default controls: all genes
+        with counts).  Writes ``obs["W_1"]`` ..., so that ``DeseqDataSet(..., design="~W_1 + condition")`` follows, and
+        returns the ``pydeseq2_amd.ruv.RuvResult`` (``W``, ``alpha``, ``normalized_counts`` and ``corrected`` as
+        DataFrames; the last two only with ``counts`` / ``corrected``).  ``corrected`` is an addition to RUVSeq's surface:
+        it returns Y' = Y - W alpha itself, on the log scale, next to the counts derived from it.  Existing ``obs`` columns
+        named ``W_<number>`` are REMOVED before the new ones are written, so that a design built from ``obs`` never mixes
+        the factors of two calls; keep a copy under another name to compare runs.  Needs size factors (``normalized``) or,
+        for "r", a finished ``deseq2()``.  Every refusal is raised before any device work."""
+        from . import ruv as _ruv
+
+        if method not in ("g", "r"):
+            raise ValueError(f"method must be 'g' (RUVg) or 'r' (RUVr), got {method!r}.")
+        if method == "g" and control_genes is None:
+            raise ValueError("ruv(method='g') needs control_genes (e.g. DeseqStats.empirical_controls()).")
+        _ruv._check_eps(epsilon)
+        sel = None if control_genes is None else self._index(control_genes, self.var_names, self.n_vars)
+        if method == "r":
+            res = self._fitted("ruv(method='r')")
+            has = np.asarray(res.non_zero, dtype=bool)
+        else:
+            res, has = self._res, None
+            if res is None:
+                if normalized and "size_factors" not in self.obs:
+                    raise ValueError("ruv(): run fit_size_factors() or deseq2() first (normalized=True needs size factors).")
+                sf = self.obs["size_factors"].to_numpy() if "size_factors" in self.obs else np.ones(self.n_obs)
+                res = type("_SizeFactorsOnly", (), {"size_factors": sf})()
+        _ruv.check_ruv_args(self.n_obs, self.n_vars, k, sel, drop, method, has)
+        r = self._pipe.ruv(res, k, sel, method, normalized, epsilon, center, drop, counts, round, corrected)
+        names = [f"W_{i + 1}" for i in range(r.W.shape[1])]
+        r.W = pd.DataFrame(r.W, index=self.obs_names, columns=names)
+        r.alpha = pd.DataFrame(r.alpha, index=names, columns=self.var_names)
+        r.genes = self.var_names[r.genes]
+        for f in ("normalized_counts", "corrected"):
+            if getattr(r, f) is not None:
+                setattr(r, f, pd.DataFrame(getattr(r, f), index=self.obs_names, columns=self.var_names))
+        for c in [c for c in self.obs.columns if re.fullmatch(r"W_[0-9]+", str(c))]:
+            del self.obs[c]
+        for n in names:
+            self.obs[n] = r.W[n].to_numpy()
+        return r
+
+    def remove_batch_effect(self, layer: str = "vst_counts", batch=None, batch2=None, covariates=None, design=None):
+        """limma's ``removeBatchEffect`` of a transformed layer before ``pca()``: ``batch`` / ``batch2``: an ``obs`` column
+        (or one label per sample) taken as a factor, ``covariates``: numeric ``obs`` columns (or an N x c matrix),
+        ``design``: the terms to protect - a formula over ``obs`` or a matrix; None: the intercept alone.  Returns the
+        N x G array and stores it as ``layers[layer + "_nobatch"]``."""
+        from . import ruv as _ruv
+
+        x = self._transformed_layer(layer, "remove_batch_effect()")
+
+        def column(v):
+            return self.obs[v].to_numpy() if isinstance(v, str) else v
+
+        cov = covariates
+        if isinstance(cov, str):
+            cov = [cov]
+        if isinstance(cov, (list, tuple)) and len(cov) and all(isinstance(c, str) for c in cov):
+            cov = self.obs[list(cov)].to_numpy(dtype=float)
+        D = None if design is None else build_design(self.obs, design, None).to_numpy()
+        b1, b2 = column(batch), column(batch2)
+        _ruv.batch_design(self.n_obs, b1, b2, cov, D)  # (refusals before any device work)
+        out = self._pipe.remove_batch_effect(x, b1, b2, cov, D)
+        self.layers[layer + "_nobatch"] = out
+        return out
+
     @property
     def non_zero_genes(self):
         return self.var_names[np.asarray(self.var["non_zero"], dtype=bool)]
@@ -1130,6 +1215,17 @@ class DeseqStats:
         self._wald_key = ("wilcoxon", self.alt_hypothesis)
         if hasattr(self, "padj"):
             del self.padj
+
+    def empirical_controls(self, min_pvalue: float = 0.1):
+        """The names of the genes whose RAW p-value exceeds ``min_pvalue`` (the workflow's "not.sig": empirical control
+        genes for ``DeseqDataSet.ruv``).  Runs the test when there are no p-values yet; NaN p-values are left out."""
+        if not 0.0 <= min_pvalue < 1.0:
+            raise ValueError(f"min_pvalue must lie in [0, 1) (got {min_pvalue}).")
+        if not hasattr(self, "p_values"):
+            self.summary()
+        pv = self.p_values.to_numpy()
+        with np.errstate(invalid="ignore"):
+            return self.dds.var_names[pv > min_pvalue]
 
     def summary(self, **kwargs) -> pd.DataFrame:
         """Wald test, Cook's filtering, adjusted p-values; returns and stores ``results_df`` (ds.py:219-299).

@@ -1,5 +1,6 @@
 // dsq_capi_dev.hip — the stages of the path on device-resident buffers (dsq_dev_*, dsq_mix_*; include/deseq_hip.h).
 #include "dsq_capi_internal.h"
+#include "dsq_proj.h"
 #include "dsq_rank.h"
 
 extern "C" {
@@ -752,6 +753,58 @@ int dsq_dev_gram_dist(dsq_ctx* ctx, const double* d_S, int N, int lds, double* d
     DSQ_CHECK_ARG(lds >= N && ldd >= N, "lds or ldd is smaller than N");
     DSQ_CHECK_ARG(d_S != nullptr && d_D != nullptr, "d_S or d_D is null");
     DSQ_HIP(dsq::launch_gram_dist(ctx->stream, d_S, N, lds, d_D, ldd));
+    return DSQ_OK;
+}
+
+int dsq_dev_log_counts(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, int N, int G, int normalized,
+                       double eps, double* d_out, int ld) {
+    DSQ_CHECK_ARG(N >= 1, "N: at least one sample");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(ldn >= N && ld >= N, "ldn or ld is smaller than N");
+    DSQ_CHECK_ARG(std::isfinite(eps) && eps > 0.0, "eps: a finite positive number");
+    DSQ_CHECK_ARG(d_out != nullptr, "d_out is null");
+    if (G == 0) return DSQ_OK;
+    DSQ_CHECK_ARG(d_y != nullptr && (d_sf != nullptr || !normalized), "d_y or d_sf is null");
+    DSQ_HIP(dsq::launch_log_counts(ctx->stream, d_y, ldn, d_sf, N, G, normalized, eps, d_out, ld));
+    return DSQ_OK;
+}
+
+int dsq_dev_nb_residuals(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, const double* d_Xt, int ldx, int P,
+                         int N, int G, const double* d_disp, const double* d_beta, int kind, double* d_out, int ld) {
+    DSQ_CHECK_ARG(N >= 1, "N: at least one sample");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(P >= 1 && P <= DSQ_MAX_P, "P out of range");
+    DSQ_CHECK_ARG(ldn >= N && ldx >= N && ld >= N, "a leading dimension is smaller than N");
+    DSQ_CHECK_ARG(kind == 0 || kind == 1, "kind: deviance (0) or Pearson (1)");
+    DSQ_CHECK_ARG(d_out != nullptr, "d_out is null");
+    if (G == 0) return DSQ_OK;
+    DSQ_CHECK_ARG(d_y != nullptr && d_sf != nullptr && d_Xt != nullptr && d_disp != nullptr && d_beta != nullptr,
+                  "an input pointer is null");
+    DSQ_HIP(dsq::launch_nb_residuals(ctx->stream, d_y, ldn, d_sf, d_Xt, ldx, P, N, G, d_disp, d_beta, kind, d_out, ld));
+    return DSQ_OK;
+}
+
+int dsq_project_plan(int N, int* waves, int* staged, size_t* lds_bytes) {
+    const dsq::ProjPlan p = dsq::proj_plan(N);
+    if (waves != nullptr) *waves = p.waves;
+    if (staged != nullptr) *staged = p.staged;
+    if (lds_bytes != nullptr) *lds_bytes = p.lds_bytes;
+    return p.waves > 0 ? DSQ_OK : DSQ_ERR_ARG;
+}
+
+int dsq_dev_project_out(dsq_ctx* ctx, const double* d_x, int ld, const double* d_Pt, const double* d_Bt, int ldp, int q,
+                        int N, int G, int post, double eps, double* d_out, int ldo, double* d_coef) {
+    DSQ_CHECK_ARG(N >= 1, "N: at least one sample");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(q >= 1 && q <= DSQ_PROJ_MAX_Q, "q: between 1 and DSQ_PROJ_MAX_Q = 64 columns");
+    DSQ_CHECK_ARG(ld >= N && ldo >= N && ldp >= N, "ld, ldo or ldp is smaller than N");
+    DSQ_CHECK_ARG(post >= 0 && post <= 2, "post: 0 (none), 1 (exp - eps) or 2 (rounded and clipped)");
+    DSQ_CHECK_ARG(post == 0 || (std::isfinite(eps) && eps > 0.0), "eps: a finite positive number");
+    DSQ_CHECK_ARG(d_out != nullptr, "d_out is null");
+    DSQ_CHECK_ARG(d_out != d_x || ldo == ld, "in place (d_out == d_x): ldo must equal ld");
+    if (G == 0) return DSQ_OK;
+    DSQ_CHECK_ARG(d_x != nullptr && d_Pt != nullptr && d_Bt != nullptr, "an input pointer is null");
+    DSQ_HIP(dsq::launch_project_out(ctx->stream, d_x, ld, d_Pt, d_Bt, ldp, q, N, G, post, eps, d_out, ldo, d_coef));
     return DSQ_OK;
 }
 

@@ -352,6 +352,15 @@ size_t sample_gram_work_doubles(int N, int K);
 hipError_t launch_sample_gram(hipStream_t st, const double* x, int layout, int N, int ld, const int32_t* sel, int K,
                               const double* mean, double* work, double* S, int lds_S);
 hipError_t launch_gram_dist(hipStream_t st, const double* S, int N, int lds_S, double* D, int ldd);
+// ---- dsq_k_proj.hip: hidden-batch factors and batch removal (dsq_proj.h), one gene per wavefront: the log counts, the
+// NB residuals of a finished fit (kind 0 deviance, 1 Pearson; beta [G][P]) and out = x - (x P) B^T with P^T, B^T [q][ldp],
+// q <= kProjMaxQ (post 0: nothing, 1: exp(.) - eps, 2: its rounded clip; out may be x; coef_out [G][q] or null)
+hipError_t launch_log_counts(hipStream_t st, const int32_t* y, int ldn, const double* sf, int N, int G, int normalized,
+                             double eps, double* out, int ld);
+hipError_t launch_nb_residuals(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* Xt, int ldx, int P,
+                               int N, int G, const double* disp, const double* beta, int kind, double* out, int ld);
+hipError_t launch_project_out(hipStream_t st, const double* x, int ld, const double* Pt, const double* Bt, int ldp, int q,
+                              int N, int G, int post, double eps, double* out, int ldo, double* coef_out);
 hipError_t launch_cooks(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* mu,
                         const double* hat, const int32_t* cell_offsets, const int32_t* cell_index,
                         int n_cells, int whole, int max_cell, const uint8_t* flags, int N, int G,

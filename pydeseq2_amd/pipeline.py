@@ -1622,6 +1622,37 @@ class DeseqPipeline:
 
         return sample_distances(self, x, genes=genes)
 
+    # ------------------------------------------------------------------ hidden batch
+    def residuals(self, res: DeseqResult, kind="deviance"):
+        """Residuals of the NB GLM (csrc/dsq_proj.h), N x G, post hoc like lrt(): from the coefficients,
+        dispersions and size factors of ``res`` and the resident ORIGINAL counts, mu = sf exp(X beta) unthresholded - not
+        from the mu_LFC layer, whose lifetime is one pass.  ``kind``: "deviance" or "pearson".  Genes without counts, or
+        with a NaN coefficient or dispersion: NaN.  (Single process, as lrt().)"""
+        from . import ruv as _ruv
+
+        return _ruv.nb_residuals(self, (self.d_y.ptr, self.ldn, self.N, self.G), res.size_factors, self.design.X, res.LFC,
+                                 res.dispersions, kind)
+
+    def ruv(self, res: DeseqResult, k, controls=None, method="g", normalized=True, epsilon=1.0, center=True, drop=0,
+            return_counts=False, round=True, corrected=False):
+        """Factors of unwanted variation of the resident original counts (RUVSeq's RUVg / RUVr; pydeseq2_amd.ruv.ruv,
+        DESIGN.md 6l) with the size factors - and, for ``method="r"``, the fit - of ``res``.  ``controls``: gene indices
+        or a mask; None with "r": all genes with counts.  Returns a pydeseq2_amd.ruv.RuvResult."""
+        from . import ruv as _ruv
+
+        fit = None
+        if method == "r":
+            fit = (self.design.X, res.LFC, res.dispersions, np.asarray(res.non_zero, dtype=bool))
+        return _ruv.ruv(self, (self.d_y.ptr, self.ldn, self.N, self.G), res.size_factors, k, controls, method, normalized,
+                        epsilon, center, drop, return_counts, round, corrected, fit)
+
+    def remove_batch_effect(self, x, batch=None, batch2=None, covariates=None, design=None):
+        """limma's removeBatchEffect of a transformed N x G matrix on this pipeline's device:
+        pydeseq2_amd.ruv.remove_batch_effect."""
+        from . import ruv as _ruv
+
+        return _ruv.remove_batch_effect(self, x, batch, batch2, covariates, design)
+
     def close(self):
         """Release the pooled device buffers."""
         if getattr(self, "_side_pending", False) or getattr(self, "_lfc_forked", False):
