@@ -238,11 +238,11 @@ int dsq_dev_trend_fit(dsq_ctx* ctx, const double* d_disp, const double* d_means,
 
 /* DeseqDataSet.fit_dispersion_prior (dds.py:866-879) + utils.mean_absolute_deviation
  * (utils.py:1210-1227): squared_logres = (MAD(log genewise - log fitted) / norm.ppf(0.75))^2 over
- * the genes with genewise >= 100*min_disp; exact medians by radix select in one workgroup.
+ * the genes with genewise >= 100*min_disp; exact medians, at every n by ONE 1024-thread workgroup that narrows
+ * in value space (block_median_values) over the residuals a wide kernel has written.  NaN if no gene enters or
+ * if more than half of the residuals are the same infinity (as the reference: inf - inf among the deviations).
  * d_gw_raw: raw genewise dispersions (clipped on the fly), d_fitted: trend values, n genes,
- * d_work: dsq_prior_mad_work_doubles(n) doubles of device scratch (n residuals; for n >= 32768 the medians
- * run as multi-workgroup radix passes — one cooperative launch with a grid barrier per pass — whose
- * global state follows the residuals). */
+ * d_work: dsq_prior_mad_work_doubles(n) doubles of device scratch (the n residuals). */
 size_t dsq_prior_mad_work_doubles(int n);
 int dsq_dev_prior_mad(dsq_ctx* ctx, const double* d_gw_raw, const double* d_fitted, int n,
                       double min_disp, double max_disp, double* d_work, double* h_squared_logres);

@@ -543,7 +543,9 @@ __global__ __launch_bounds__(1024) void k_prior_mad(const double* __restrict__ r
     block_median_values<1024>([&](auto fn) { walk(fn); }, S, center, M);
     block_median_values<1024>([&](auto fn) { walk([&](double r) { fn(fabs(r - center)); }); }, S, mad, M2);
     if (tid == 0) {
-        const double m = mad / 0.67448975019608171;  // norm.ppf(0.75)
+        // (an infinite center - more than half of the residuals at one infinity - makes the deviations of those residuals
+        // inf - inf = NaN, and the reference's second median is NaN then; the select leaves a NaN out and would say inf)
+        const double m = (fabs(center) < INFINITY) ? mad / 0.67448975019608171 : NAN;  // norm.ppf(0.75)
         out[0] = m * m;
         out[1] = (double)M;
     }
@@ -1528,8 +1530,9 @@ hipError_t launch_scatter_rows(hipStream_t st, const double* src, const int32_t*
 
 // ------------------------------------------------------------------ distributed size factors
 // Multi-GPU layout: every rank owns a gene shard, but a sample's size factor is the median over
-// ALL genes.  The radix select of k_row_median is therefore split into per-pass kernels whose
-// per-sample 256-bin digit histograms are summed across ranks (RCCL all-reduce) between passes.
+// ALL genes.  The radix select of k_row_median_c is therefore split into per-pass kernels whose
+// per-sample 256-bin digit histograms are summed across ranks (RCCL all-reduce) between passes; the keys are the
+// compacted ones of k_ratio_keys_c (k_ratio_keys / k_row_median, the uncompacted pair, have no caller in the package).
 // state (per sample): prefix[2] (u64), rank[2] (u32) for the two middle order statistics.
 struct SfState {
     unsigned long long* prefix;  // [2][N]

@@ -33,7 +33,8 @@ _vp = C.c_void_p
 # ------------------------------------------------------------------ protocol (backend agnostic)
 def median_select_protocol(ops, allreduce_sum):
     """Distributed per-sample median: `ops` provides the local passes, `allreduce_sum(x)` returns
-    the element-wise sum of x over all ranks (in place is fine).  Mirrors k_row_median."""
+    the element-wise sum of x over all ranks (in place is fine).  The radix select of k_row_median_c (both middle
+    ranks tracked in the same sweeps), with 8-bit digits and the digit histograms summed over the ranks."""
     total = allreduce_sum(ops.count())
     ops.init(total)
     for shift in range(56, -8, -8):

@@ -853,9 +853,9 @@ def test_size_factors_register_and_key_matrix_paths(G, N, zero_frac, count_dtype
 
 @pytest.mark.parametrize("n", [5000, 40000, 300001])
 def test_prior_mad_kernel_vs_numpy(n):
-    """dsq_dev_prior_mad (one workgroup below 32768 genes, multi-workgroup radix passes above — the
-    gathered vectors of the multi-GPU layout) against numpy medians, with NaN padding, genes below
-    the 100*min_disp threshold and ties."""
+    """dsq_dev_prior_mad (one 1024-thread workgroup that narrows in value space, at every n - also for the
+    gathered vectors of the multi-GPU layout) against numpy medians, with NaN padding and genes below
+    the 100*min_disp threshold; the branches of the selection and exact ties: tests/test_gpu_medians.py."""
     import ctypes as C
 
     from pydeseq2_amd._lib import Context, DeviceArray
