@@ -391,10 +391,14 @@ class DeviceArray:
     def from_host(cls, ctx, arr, ld=None):
         arr = np.ascontiguousarray(arr)
         self = cls(ctx, arr.shape, arr.dtype, ld)
-        if arr.ndim == 2 and self.ld != arr.shape[1]:
-            ctx.h2d_rows(self.ptr, arr, self.ld)
-        else:
-            ctx.h2d(self.ptr, arr)
+        try:
+            if arr.ndim == 2 and self.ld != arr.shape[1]:
+                ctx.h2d_rows(self.ptr, arr, self.ld)
+            else:
+                ctx.h2d(self.ptr, arr)
+        except BaseException:  # (a copy that fails leaves no allocation behind)
+            self.free()
+            raise
         return self
 
     def to_host(self):
@@ -413,6 +417,74 @@ class DeviceArray:
             self.free()
         except Exception:
             pass
+
+
+class DeviceScope:
+    """Owner of the device buffers of one post-hoc call: a list and a ``finally``.
+
+        with DeviceScope(ctx) as s:
+            d_sf = s.upload(sf)
+            d_out = s.empty((Gn, N), np.float64)
+
+    On exit - with or without an exception - the context is synchronised once, then everything the scope made or adopted
+    is freed in reverse order of creation.  An array it did not make or adopt (the caller's DeviceArray, a pipeline's
+    resident buffers) is never freed.  An exception of the body wins over one of ``sync()`` / ``free()``; a failing
+    ``free()`` does not keep the others from running, and the first such error is raised when the body raised nothing."""
+
+    def __init__(self, ctx):
+        self.ctx, self._owned, self._open = ctx, [], True
+
+    def __enter__(self):
+        return self
+
+    def adopt(self, d):
+        """Take over a DeviceArray made elsewhere (what a helper returns for its caller to free)."""
+        self._owned.append(d)
+        return d
+
+    def empty(self, shape, dtype, ld=None):
+        return self.adopt(DeviceArray(self.ctx, shape, dtype, ld))
+
+    def upload(self, a, dtype=None, ld=None):
+        return self.adopt(DeviceArray.from_host(self.ctx, np.ascontiguousarray(a, dtype=dtype), ld))
+
+    def __exit__(self, exc_type, exc, tb):
+        if not self._open:
+            return False
+        self._open = False
+        errors = []
+        for step in [self.ctx.sync] + [d.free for d in reversed(self._owned)]:
+            try:
+                step()
+            except Exception as e:
+                errors.append(e)
+        self._owned = []
+        if errors and exc_type is None:
+            raise errors[0]
+        return False
+
+
+def split(pipe_or_ctx):
+    """A post-hoc call runs on a DeseqPipeline or on a bare Context: -> (the pipeline or None, the context)."""
+    return (pipe_or_ctx if hasattr(pipe_or_ctx, "_k") else None), getattr(pipe_or_ctx, "ctx", pipe_or_ctx)
+
+
+def launch(pipe_or_ctx, name, genes, cname, *args):
+    """Launch ``cname`` through the pipeline's ``_k`` (which times it under ``name`` when asked to), else ``ctx.call``."""
+    pipe, ctx = split(pipe_or_ctx)
+    if pipe is not None:
+        pipe._k(name, genes, cname, *args)
+    else:
+        ctx.call(cname, *args)
+
+
+def gather_rows_i32(scope, ctx, d_src_ptr, ld, idx, N):
+    """The rows ``idx`` of the int32 device matrix at ``d_src_ptr`` (pitch ``ld``, N columns used) -> DeviceArray
+    [len(idx)][ld] owned by ``scope``."""
+    d_idx = scope.upload(idx, dtype=np.int32)
+    d = scope.empty((len(idx), N), np.int32, ld=ld)
+    ctx.call("dsq_dev_gather_rows_i32", _vp(d_src_ptr), ld, _vp(d_idx.ptr), len(idx), N, _vp(d.ptr))
+    return d
 
 
 class _PinnedPool:

@@ -70,9 +70,8 @@ def ash(pipe, lfc, se, grids=None, max_iter=MAX_ITER):
     """Adaptive shrinkage of K contrasts (``lfc``, ``se``: K x G, or one vector each) on the device of ``pipe`` (a
     DeseqPipeline, or a ``_lib.Context``): one upload, dsq_dev_ash (the fit and the posterior kernel), one download.
     ``grids``: the K grids (default: ``mixsd_grid`` of each contrast).  A contrast without used genes gets NaN everywhere."""
-    from ._lib import DeviceArray
+    from ._lib import DeviceScope, launch, split
 
-    ctx = getattr(pipe, "ctx", pipe)
     b = np.ascontiguousarray(np.atleast_2d(np.asarray(lfc, dtype=np.float64)))
     s = np.ascontiguousarray(np.atleast_2d(np.asarray(se, dtype=np.float64)))
     if b.shape != s.shape or b.ndim != 2:
@@ -104,24 +103,16 @@ def ash(pipe, lfc, se, grids=None, max_iter=MAX_ITER):
     n_out_d = K * ldm + 3 * K * G + 2 * K
     h_out = np.zeros(8 * n_out_d + 4 * K + K, np.uint8)
     h_out[:8 * n_out_d].view(np.float64)[:] = np.nan  # (a skipped contrast's outputs are not written)
-    d_in = DeviceArray.from_host(ctx, h_in)
-    d_out = DeviceArray.from_host(ctx, h_out)
-    try:
+    with DeviceScope(split(pipe)[1]) as sc:
+        d_in, d_out = sc.upload(h_in), sc.upload(h_out)
         i0, o0 = d_in.ptr, d_out.ptr
         o_pi, o_pm, o_ps, o_fs = o0, o0 + 8 * K * ldm, o0 + 8 * (K * ldm + K * G), o0 + 8 * (K * ldm + 2 * K * G)
         o_kkt = o0 + 8 * (K * ldm + 3 * K * G)
         o_ll, o_it = o_kkt + 8 * K, o0 + 8 * n_out_d
-        args = (_vp(i0), _vp(i0 + 8 * K * G), G, G, K, _vp(i0 + 16 * K * G), _vp(i0 + 8 * in_d.size), ldm, int(max_iter),
-                _vp(o_pi), _vp(o_pm), _vp(o_ps), _vp(o_fs), _vp(o_it), _vp(o_it + 4 * K), _vp(o_kkt), _vp(o_ll))
-        if hasattr(pipe, "_k"):
-            pipe._k("ash", K * G, "dsq_dev_ash", *args)
-        else:
-            ctx.call("dsq_dev_ash", *args)
+        launch(pipe, "ash", K * G, "dsq_dev_ash", _vp(i0), _vp(i0 + 8 * K * G), G, G, K, _vp(i0 + 16 * K * G),
+               _vp(i0 + 8 * in_d.size), ldm, int(max_iter), _vp(o_pi), _vp(o_pm), _vp(o_ps), _vp(o_fs), _vp(o_it),
+               _vp(o_it + 4 * K), _vp(o_kkt), _vp(o_ll))
         out = d_out.to_host()
-    finally:
-        ctx.sync()
-        d_in.free()
-        d_out.free()
     od = out[:8 * n_out_d].view(np.float64)
     pi = od[:K * ldm].reshape(K, ldm)
     res.post_mean, res.post_sd, res.lfsr = (od[K * ldm + j * K * G:K * ldm + (j + 1) * K * G].reshape(K, G).copy()

@@ -17,7 +17,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import GENE_MAJOR, SAMPLE_MAJOR, DeviceArray
+from ._lib import GENE_MAJOR, SAMPLE_MAJOR, DeviceArray, DeviceScope, launch, split
 
 _vp = C.c_void_p
 
@@ -85,10 +85,10 @@ def pca_from_gram(S, n_components=None, genes=None):
 
 
 class _Resident:
-    """The matrix on the device: a host N x G array is uploaded once (sample-major), a DeviceArray is taken as it is."""
+    """The matrix on the device: a host N x G array is uploaded once (sample-major) into the scope that first asks for its
+    pointer, a DeviceArray is taken as it is (and stays the caller's)."""
 
-    def __init__(self, ctx, x, layout):
-        self.own = None
+    def __init__(self, x, layout):
         if isinstance(x, DeviceArray):
             if len(x.shape) != 2 or x.dtype != np.float64:
                 raise ValueError("a DeviceArray input must be a two-dimensional float64 matrix.")
@@ -105,52 +105,34 @@ class _Resident:
             self.N, self.G = a.shape
             self.ld = self.G
 
-    def ptr(self, ctx):
+    def ptr(self, s):
         if self.dev is None:
-            self.own = self.dev = DeviceArray.from_host(ctx, self.host)
+            self.dev = s.upload(self.host)
         return self.dev.ptr
 
-    def free(self):
-        if self.own is not None:
-            self.own.free()
-            self.own = None
 
-
-def _call(pipe, name, genes, cname, *args):
-    if hasattr(pipe, "_k"):
-        pipe._k(name, genes, cname, *args)
-    else:
-        getattr(pipe, "ctx", pipe).call(cname, *args)
-
-
-def _meanvar(pipe, ctx, R, want_var):
-    """-> (device means, host variances or None)"""
-    d_mv = DeviceArray(ctx, (2 if want_var else 1, R.G), np.float64)
-    _call(pipe, "row_meanvar", R.G, "dsq_dev_row_meanvar", _vp(R.ptr(ctx)), R.layout, R.N, R.G, R.ld, _vp(d_mv.ptr),
-          _vp(d_mv.ptr + 8 * R.G) if want_var else None)
+def _meanvar(who, s, R, want_var):
+    """-> (device means, owned by the scope s; host variances or None)"""
+    d_mv = s.empty((2 if want_var else 1, R.G), np.float64)
+    launch(who, "row_meanvar", R.G, "dsq_dev_row_meanvar", _vp(R.ptr(s)), R.layout, R.N, R.G, R.ld, _vp(d_mv.ptr),
+           _vp(d_mv.ptr + 8 * R.G) if want_var else None)
     rv = None
     if want_var:
         rv = np.empty(R.G)
-        ctx.d2h(rv, d_mv.ptr + 8 * R.G)
+        s.ctx.d2h(rv, d_mv.ptr + 8 * R.G)
     return d_mv, rv
 
 
-def _gram(pipe, ctx, R, sel, d_mean):
-    """-> the N x N Gram on the device (a DeviceArray the caller frees)"""
+def _gram(who, s, R, sel, d_mean):
+    """-> the N x N Gram on the device (a DeviceArray of the scope s)"""
     K = R.G if sel is None else len(sel)
-    d_S = DeviceArray(ctx, (R.N, R.N), np.float64)
-    d_sel = DeviceArray.from_host(ctx, np.ascontiguousarray(sel, dtype=np.int32)) if sel is not None and K else None
-    n_work = int(ctx.lib.dsq_sample_gram_work_doubles(R.N, K)) if R.G else 0
-    d_work = DeviceArray(ctx, n_work, np.float64) if n_work else None
-    try:
-        _call(pipe, "sample_gram", K, "dsq_dev_sample_gram", _vp(R.ptr(ctx)) if R.G else None, R.layout, R.N, R.G, R.ld,
-              _vp(d_sel.ptr) if d_sel is not None else None, K, _vp(d_mean.ptr) if d_mean is not None else None,
-              _vp(d_work.ptr) if d_work is not None else None, _vp(d_S.ptr), R.N)
-    finally:
-        ctx.sync()
-        for d in (d_sel, d_work):
-            if d is not None:
-                d.free()
+    d_S = s.empty((R.N, R.N), np.float64)
+    d_sel = s.upload(sel, dtype=np.int32) if sel is not None and K else None
+    n_work = int(s.ctx.lib.dsq_sample_gram_work_doubles(R.N, K)) if R.G else 0
+    d_work = s.empty(n_work, np.float64) if n_work else None
+    launch(who, "sample_gram", K, "dsq_dev_sample_gram", _vp(R.ptr(s)) if R.G else None, R.layout, R.N, R.G, R.ld,
+           _vp(d_sel.ptr) if d_sel is not None else None, K, _vp(d_mean.ptr) if d_mean is not None else None,
+           _vp(d_work.ptr) if d_work is not None else None, _vp(d_S.ptr), R.N)
     return d_S
 
 
@@ -168,49 +150,29 @@ def _gene_list(genes, G):
 def row_variances(ctx, x, layout=SAMPLE_MAJOR):
     """Per-gene variance over the samples (R's ``rowVars``: two-pass, divisor N - 1; one sample: NaN) of ``x``: a host
     N x G array, or a ``DeviceArray`` in ``layout`` (SAMPLE_MAJOR: N x G, GENE_MAJOR: G x N)."""
-    pipe, ctx = ctx, getattr(ctx, "ctx", ctx)
-    R = _Resident(ctx, x, layout)
+    R = _Resident(x, layout)
     if R.N < 1:
         raise ValueError("row_variances(): at least one sample is needed.")
     if R.G == 0:
         return np.zeros(0)
-    try:
-        d_mv, rv = _meanvar(pipe, ctx, R, True)
-        d_mv.free()
-    finally:
-        ctx.sync()
-        R.free()
-    return rv
+    with DeviceScope(split(ctx)[1]) as s:
+        return _meanvar(ctx, s, R, True)[1]
 
 
-def _gram_on_device(pipe, ctx, R, sel, center):
-    d_mean = None
-    try:
-        if center and R.G:
-            d_mean, _ = _meanvar(pipe, ctx, R, False)
-        return _gram(pipe, ctx, R, sel, d_mean)
-    finally:
-        if d_mean is not None:
-            ctx.sync()
-            d_mean.free()
+def _gram_on_device(who, s, R, sel, center):
+    d_mean = _meanvar(who, s, R, False)[0] if center and R.G else None
+    return _gram(who, s, R, sel, d_mean)
 
 
 def sample_gram(ctx, x, genes=None, center=True, layout=SAMPLE_MAJOR):
     """The N x N Gram matrix ``X~ X~^T`` of the samples over ``genes`` (indices, in the order given; None: all), each gene
     centred by its mean over the samples unless ``center=False``.  Exactly symmetric."""
-    pipe, ctx = ctx, getattr(ctx, "ctx", ctx)
-    R = _Resident(ctx, x, layout)
+    R = _Resident(x, layout)
     if R.N < 1:
         raise ValueError("sample_gram(): at least one sample is needed.")
     sel = _gene_list(genes, R.G)
-    try:
-        d_S = _gram_on_device(pipe, ctx, R, sel, center)
-        S = d_S.to_host()
-        d_S.free()
-    finally:
-        ctx.sync()
-        R.free()
-    return S
+    with DeviceScope(split(ctx)[1]) as s:
+        return _gram_on_device(ctx, s, R, sel, center).to_host()
 
 
 def pca(ctx, x, ntop=500, n_components=None, layout=SAMPLE_MAJOR):
@@ -219,23 +181,14 @@ def pca(ctx, x, ntop=500, n_components=None, layout=SAMPLE_MAJOR):
     components (a partial eigensolve); None: all N.  Returns a PcaResult; ``genes`` holds the indices of the genes used in
     order of decreasing variance.  ValueError: fewer than two samples, ``ntop < 1``, ``n_components`` outside
     1 ... min(N, K), a non-finite row variance."""
-    pipe, ctx = ctx, getattr(ctx, "ctx", ctx)
-    R = _Resident(ctx, x, layout)
+    R = _Resident(x, layout)
     check_pca_args(R.N, R.G, ntop, n_components)
     if R.G == 0:
         raise ValueError("pca(): the matrix has no genes.")
-    d_mv = None
-    try:
-        d_mv, rv = _meanvar(pipe, ctx, R, True)
+    with DeviceScope(split(ctx)[1]) as s:
+        d_mv, rv = _meanvar(ctx, s, R, True)
         sel = select_genes(rv, ntop)
-        d_S = _gram(pipe, ctx, R, None if ntop is None else sel, d_mv)
-        S = d_S.to_host()
-        d_S.free()
-    finally:
-        ctx.sync()
-        if d_mv is not None:
-            d_mv.free()
-        R.free()
+        S = _gram(ctx, s, R, None if ntop is None else sel, d_mv).to_host()
     return pca_from_gram(S, n_components, sel)
 
 
@@ -243,19 +196,12 @@ def sample_distances(ctx, x, genes=None, layout=SAMPLE_MAJOR):
     """Euclidean distances between the samples (R's ``dist``) over ``genes`` (None: all), N x N with a zero diagonal, from
     the centred Gram (the centring cancels in a difference and conditions the Gram better); see the module docstring
     for the accuracy."""
-    pipe, ctx = ctx, getattr(ctx, "ctx", ctx)
-    R = _Resident(ctx, x, layout)
+    R = _Resident(x, layout)
     if R.N < 1:
         raise ValueError("sample_distances(): at least one sample is needed.")
     sel = _gene_list(genes, R.G)
-    try:
-        d_S = _gram_on_device(pipe, ctx, R, sel, True)
-        d_D = DeviceArray(ctx, (R.N, R.N), np.float64)
-        _call(pipe, "gram_dist", R.N, "dsq_dev_gram_dist", _vp(d_S.ptr), R.N, R.N, _vp(d_D.ptr), R.N)
-        D = d_D.to_host()
-        d_S.free()
-        d_D.free()
-    finally:
-        ctx.sync()
-        R.free()
-    return D
+    with DeviceScope(split(ctx)[1]) as s:
+        d_S = _gram_on_device(ctx, s, R, sel, True)
+        d_D = s.empty((R.N, R.N), np.float64)
+        launch(ctx, "gram_dist", R.N, "dsq_dev_gram_dist", _vp(d_S.ptr), R.N, R.N, _vp(d_D.ptr), R.N)
+        return d_D.to_host()

@@ -26,6 +26,7 @@ from scipy.stats import f as f_dist
 from . import trend as _trend
 from ._design import DesignPack, pad16
 from ._lib import ALT, HOOK_FN, I32, I64, SAMPLE_MAJOR, Context, DeviceArray, DsqCells, _PinnedPool, _PinnedSlab  # noqa: F401
+from .lrt import check_reduced_design  # noqa: F401  (its home is lrt.py; importable from here as before)
 
 import ctypes as C
 import functools
@@ -76,29 +77,6 @@ def _trigamma(x):
     from scipy.special import polygamma
 
     return float(polygamma(1, x))
-
-
-def check_reduced_design(X, reduced_design):
-    """The reduced design of a likelihood-ratio test against the full design X, as a float matrix - or a ValueError that
-    names what is wrong with it.  Host only."""
-    X = np.asarray(X, dtype=np.float64)
-    Xr = np.asarray(reduced_design, dtype=np.float64)
-    N, P = X.shape
-    if Xr.ndim != 2:
-        raise ValueError("The reduced design must be a samples x columns matrix.")
-    if Xr.shape[0] != N:
-        raise ValueError(f"The reduced design has {Xr.shape[0]} rows; the data set has {N} samples.")
-    if not 1 <= Xr.shape[1] <= P - 1:
-        raise ValueError(f"The reduced design must have between 1 and {P - 1} columns (fewer than the full design's "
-                         f"{P}); it has {Xr.shape[1]}.")
-    if np.isnan(Xr).any():
-        raise ValueError("NaNs are not allowed in the reduced design.")
-    if np.linalg.matrix_rank(Xr) != Xr.shape[1]:
-        raise ValueError("The reduced design is rank deficient (its columns are linearly dependent).")
-    if np.linalg.matrix_rank(np.hstack([Xr, X])) != np.linalg.matrix_rank(X):
-        raise ValueError("The reduced design is not nested in the full design: its columns must lie in the span of the "
-                         "full design's columns.")
-    return np.ascontiguousarray(Xr)
 
 
 class _Respeculate(Exception):
@@ -1332,254 +1310,49 @@ class DeseqPipeline:
         if d.size:
             self.ctx.h2d(st.S["disp"].ptr, d)
 
+    # ------------------------------------------------------------------ post-hoc calls: delegates
     def vst_transform(self, size_factors, trend_coeffs=None, mean_disp=None):
-        """Variance-stabilised counts N x G (dds.py:440-514) from the resident raw counts."""
-        ctx = self.ctx
-        d_sf = DeviceArray.from_host(ctx, np.ascontiguousarray(size_factors, dtype=np.float64))
-        d_out = DeviceArray(ctx, (self.N, self.G), np.float64)
-        if trend_coeffs is not None:
-            mode, a0, a1 = 0, float(trend_coeffs[0]), float(trend_coeffs[1])
-        else:
-            mode, a0, a1 = 1, float(mean_disp), 0.0
-        ctx.call("dsq_dev_vst", _vp(self.d_raw.ptr), self._count_type, self.N, self.G, _vp(d_sf.ptr), mode,
-                 c_double(a0), c_double(a1), _vp(d_out.ptr))
-        return d_out.to_host()
+        """Variance-stabilised counts N x G (dds.py:440-514) from the resident raw counts: pydeseq2_amd.vst."""
+        from .vst import vst_transform
+
+        return vst_transform(self, size_factors, trend_coeffs, mean_disp)
 
     def vst_transform_new(self, counts, logmeans, filtered, trend_coeffs=None, mean_disp=None):
-        """Variance-stabilised NEW samples (M x G): their size factors are the medians of
-        log(count) - training logmeans over the training-usable genes (preprocessing.py:59-102 as called from
-        dds.py:471-484), then the same closed form."""
-        from ._lib import I32, I64
+        """Variance-stabilised NEW samples (M x G) with the training fit: pydeseq2_amd.vst.vst_transform_new."""
+        from .vst import vst_transform_new
 
-        ctx = self.ctx
-        counts = np.ascontiguousarray(counts if counts.dtype in (np.int32, np.int64) else counts.astype(np.int64))
-        M, G = counts.shape
-        if G != self.G:
-            raise ValueError("new counts must have the genes of the fitted dataset")
-        ct = I32 if counts.dtype == np.int32 else I64
-        d_c = DeviceArray.from_host(ctx, counts)
-        lm = np.where(np.asarray(filtered, dtype=bool), np.asarray(logmeans, dtype=float), -np.inf)
-        d_lm = DeviceArray.from_host(ctx, np.ascontiguousarray(lm))
-        d_work = DeviceArray(ctx, (ctx.lib.dsq_size_factors_work_doubles(M, G),), np.float64)
-        d_sf = DeviceArray(ctx, (M,), np.float64)
-        ctx.call("dsq_dev_size_factors_new", _vp(d_c.ptr), ct, M, G, _vp(d_lm.ptr), None, _vp(d_work.ptr), _vp(d_sf.ptr))
-        d_out = DeviceArray(ctx, (M, G), np.float64)
-        if trend_coeffs is not None:
-            mode, a0, a1 = 0, float(trend_coeffs[0]), float(trend_coeffs[1])
-        else:
-            mode, a0, a1 = 1, float(mean_disp), 0.0
-        ctx.call("dsq_dev_vst", _vp(d_c.ptr), ct, M, G, _vp(d_sf.ptr), mode, c_double(a0), c_double(a1), _vp(d_out.ptr))
-        return d_out.to_host()
+        return vst_transform_new(self, counts, logmeans, filtered, trend_coeffs, mean_disp)
 
     def wald(self, res: DeseqResult, contrast, lfc_null=0.0, alt_hypothesis=None, lfc=None, ridge=None):
-        """Wald test only (ds.py:303-360) on the dispersions / LFCs of ``res`` (e.g. another contrast or
-        alternative hypothesis after ``deseq2()``; ``lfc``: other coefficients, e.g. shrunk ones; ``ridge``: other
-        ridge matrix, ds.py:326-334).  Returns (pvalue, stat, lfcSE), NaN for all-zero genes."""
-        if alt_hypothesis not in ALT:
-            raise KeyError(alt_hypothesis)
-        if lfc_null < 0 and alt_hypothesis in {"greaterAbs", "lessAbs"}:
-            raise ValueError(f"The alternative hypothesis being {alt_hypothesis}, please provide a "
-                             f"positive lfc_null value (got {lfc_null}).")
-        G, N, P, D = self.G, self.N, self.P, self.design
-        contrast = np.ascontiguousarray(contrast, dtype=np.float64)
-        ridge = np.ascontiguousarray(np.diag(np.repeat(1e-6, P)) if ridge is None else ridge, dtype=np.float64)
-        ctx = self.ctx
-        d_sf = DeviceArray.from_host(ctx, np.ascontiguousarray(res.size_factors, dtype=np.float64))
-        d_beta = DeviceArray.from_host(ctx, np.ascontiguousarray(res.LFC if lfc is None else lfc, dtype=np.float64))
-        d_disp = DeviceArray.from_host(ctx, np.ascontiguousarray(res.dispersions, dtype=np.float64))
-        d_out = DeviceArray(ctx, (3 * G,), np.float64)
-        ctx.call("dsq_dev_wald", None, self.ldn, _vp(d_sf.ptr), _vp(self.d_Xt.ptr), D.ldx, N, G, P, _vp(d_disp.ptr),
-                 _vp(d_beta.ptr), _vp(ridge.ctypes.data), _vp(contrast.ctypes.data), c_double(np.log(2) * lfc_null),
-                 ALT[alt_hypothesis], _vp(d_out.ptr), _vp(d_out.ptr + 8 * G), _vp(d_out.ptr + 16 * G))
-        o = d_out.to_host()
-        pv, st, se = o[:G].copy(), o[G:2 * G].copy(), o[2 * G:].copy()
-        z = np.asarray(res.new_all_zeroes, dtype=bool)
-        if z.any():  # ds.py:357-360
-            se[z], st[z], pv[z] = 0.0, 0.0, 1.0
-        return pv, st, se
+        """Wald test only (ds.py:303-360) on the dispersions / LFCs of ``res`` (e.g. another contrast or alternative
+        hypothesis after ``deseq2()``; ``lfc``: other coefficients, e.g. shrunk ones; ``ridge``: other ridge matrix).
+        Returns (pvalue, stat, lfcSE), NaN for all-zero genes: pydeseq2_amd.wald.wald."""
+        from .wald import wald
+
+        return wald(self, res, contrast, lfc_null, alt_hypothesis, lfc, ridge)
 
     def wald_multi(self, res: DeseqResult, contrasts, lfc_null=0.0, alt_hypothesis=None, lfc=None, ridge=None):
-        """Wald tests of K contrasts of the same fit (``contrasts``: K x P) in one launch: per gene X^T W X is accumulated
-        and factored once (k_wald_multi / k_wald_multi_wide), only the per-contrast tail repeats.  One upload of size
-        factors, coefficients and dispersions, one download.  Arguments as wald(); returns (pvalue, stat, lfcSE), each
-        K x G, row k what wald(res, contrasts[k], ...) returns.  (Single process: DistributedDeseq has no counterpart.)"""
-        if alt_hypothesis not in ALT:
-            raise KeyError(alt_hypothesis)
-        if lfc_null < 0 and alt_hypothesis in {"greaterAbs", "lessAbs"}:
-            raise ValueError(f"The alternative hypothesis being {alt_hypothesis}, please provide a "
-                             f"positive lfc_null value (got {lfc_null}).")
-        G, N, P, D = self.G, self.N, self.P, self.design
-        contrasts = np.ascontiguousarray(contrasts, dtype=np.float64)
-        if contrasts.ndim != 2:
-            raise ValueError("wald_multi() takes a K x P matrix of contrasts; use wald() for a single contrast vector.")
-        K = contrasts.shape[0]
-        if K < 1 or contrasts.shape[1] != P:
-            raise ValueError(f"contrasts must be K x {P} with K >= 1 (got {contrasts.shape[0]} x {contrasts.shape[1]}).")
-        ridge = np.ascontiguousarray(np.diag(np.repeat(1e-6, P)) if ridge is None else ridge, dtype=np.float64)
-        ctx = self.ctx
-        d_sf = DeviceArray.from_host(ctx, np.ascontiguousarray(res.size_factors, dtype=np.float64))
-        d_beta = DeviceArray.from_host(ctx, np.ascontiguousarray(res.LFC if lfc is None else lfc, dtype=np.float64))
-        d_disp = DeviceArray.from_host(ctx, np.ascontiguousarray(res.dispersions, dtype=np.float64))
-        d_con = DeviceArray.from_host(ctx, contrasts)
-        d_out = DeviceArray(ctx, (3 * G * K,), np.float64)
-        ctx.call("dsq_dev_wald_multi", None, self.ldn, _vp(d_sf.ptr), _vp(self.d_Xt.ptr), D.ldx, N, G, P, _vp(d_disp.ptr),
-                 _vp(d_beta.ptr), _vp(ridge.ctypes.data), _vp(d_con.ptr), K, c_double(np.log(2) * lfc_null),
-                 ALT[alt_hypothesis], _vp(d_out.ptr), _vp(d_out.ptr + 8 * G * K), _vp(d_out.ptr + 16 * G * K))
-        o = d_out.to_host().reshape(3, G, K)
-        pv, st, se = (np.ascontiguousarray(o[i].T) for i in range(3))
-        z = np.asarray(res.new_all_zeroes, dtype=bool)
-        if z.any():  # ds.py:357-360
-            se[:, z], st[:, z], pv[:, z] = 0.0, 0.0, 1.0
-        return pv, st, se
+        """Wald tests of K contrasts of the same fit (``contrasts``: K x P) in one launch; returns (pvalue, stat, lfcSE),
+        each K x G, row k what wald(res, contrasts[k], ...) returns: pydeseq2_amd.wald.wald_multi.  (Single process:
+        DistributedDeseq has no counterpart.)"""
+        from .wald import wald_multi
 
-    # ------------------------------------------------------------------ likelihood-ratio test
+        return wald_multi(self, res, contrasts, lfc_null, alt_hypothesis, lfc, ridge)
+
     def lrt(self, res: DeseqResult, reduced_design):
         """Likelihood-ratio test of a nested reduced design (DESeq2's nbinomLRT) on the dispersions / LFCs of ``res``,
-        post hoc like wald().  The reduced design is fitted by the IRLS launcher of the LFC stage (dsq_dev_lfc_fit2
-        without epilogue, the reduced design's own DesignPack and cells) with the final dispersions, size factors and
-        settings of fit_LFC, on the counts the final LFC was fitted on - the replaced counts of the last pass for the
-        refitted genes - and k_lrt scores the two fits (csrc/dsq_lrt.h).
-        Returns (pvalue, stat, reduced_LFC [G x P_reduced, natural log], reduced_converged); NaN for all-zero genes;
-        genes whose counts all became zero in the refit: stat 0, pvalue 1 (the Wald rule, ds.py:357-360) and reduced_LFC 0."""
-        Xr = check_reduced_design(self.design.X, reduced_design)
-        G, N, ctx = self.G, self.N, self.ctx
-        Dr = DesignPack(Xr, self.min_replicates)
-        Pr = Dr.P
-        nz = np.asarray(res.non_zero, dtype=bool)
-        nzi = np.nonzero(nz)[0]
-        Gn = len(nzi)
-        pv, stt = np.full(G, np.nan), np.full(G, np.nan)
-        beta_r, conv_r = np.full((G, Pr), np.nan), np.full(G, np.nan)
-        refitted = np.asarray(res.refitted, dtype=bool) if res.refitted is not None else np.zeros(G, dtype=bool)
-        keep = self._replace_keep
-        if refitted.any() and (keep is None or keep["naz"] is None):
-            raise RuntimeError("lrt(): the replaced counts of this result's refit are gone (another pass has run since)")
-        held = []  # device arrays of this call
+        post hoc like wald().  Returns (pvalue, stat, reduced_LFC [G x P_reduced, natural log], reduced_converged):
+        pydeseq2_amd.lrt.lrt."""
+        from .lrt import lrt
 
-        def dev(a):
-            held.append(DeviceArray.from_host(ctx, np.ascontiguousarray(a)))
-            return held[-1]
+        return lrt(self, res, reduced_design)
 
-        try:
-            d_sf = dev(np.asarray(res.size_factors, dtype=np.float64))
-            d_Xr, d_pinv = dev(Dr.Xt), dev(Dr.pinvXt)
-            cells = None
-            if Dr.cell_path and not os.environ.get("DSQ_NO_CELL_PATH"):
-                cells = DsqCells(dev(Dr.cell_of).ptr, dev(Dr.Xc).ptr, dev(Dr.XXc).ptr, int(Dr.n_design_cells))
-
-            def run(d_y, idx):
-                """Reduced fit + statistic of the rows of d_y, which are the genes idx -> host vectors."""
-                Gs = len(idx)
-                d_bf = dev(np.asarray(res.LFC, dtype=np.float64)[idx])
-                d_disp = dev(np.asarray(res.dispersions, dtype=np.float64)[idx])
-                d_br, d_cv = DeviceArray(ctx, (Gs, Pr), np.float64), DeviceArray(ctx, (Gs,), np.uint8)
-                d_out = DeviceArray(ctx, (2 * Gs,), np.float64)
-                held.extend([d_br, d_cv, d_out])
-                self._k("lrt_reduced_fit", Gs, "dsq_dev_lfc_fit2", _vp(d_y.ptr), self.ldn, _vp(d_sf.ptr), _vp(d_Xr.ptr),
-                        _vp(d_pinv.ptr), Dr.ldx, N, Gs, Pr, int(Dr.full_rank), _vp(d_disp.ptr), c_double(self.min_mu),
-                        c_double(self.beta_tol), c_double(-30.0), c_double(30.0), self.irls_maxiter, _vp(d_br.ptr), None,
-                        None, _vp(d_cv.ptr), None, C.byref(cells) if cells is not None else None,
-                        None, None, c_double(0.0), None, None, None, None, None,
-                        None, None, c_double(0.0), 0, None, None, None, None, 0)
-                self._k("lrt", Gs, "dsq_dev_lrt", _vp(d_y.ptr), self.ldn, _vp(d_sf.ptr), _vp(self.d_Xt.ptr),
-                        self.design.ldx, self.P, _vp(d_Xr.ptr), Dr.ldx, Pr, N, Gs, _vp(d_disp.ptr), _vp(d_bf.ptr),
-                        _vp(d_br.ptr), _vp(d_out.ptr), _vp(d_out.ptr + 8 * Gs))
-                o = d_out.to_host()
-                return o[Gs:], o[:Gs], d_br.to_host(), d_cv.to_host().astype(float)
-
-            if Gn > 0:
-                if Gn == G:
-                    d_y = self.d_y
-                else:
-                    d_idx = dev(nzi.astype(np.int32))
-                    d_y = DeviceArray(ctx, (Gn, N), np.int32, ld=self.ldn)
-                    held.append(d_y)
-                    ctx.call("dsq_dev_gather_rows_i32", _vp(self.d_y.ptr), self.ldn, _vp(d_idx.ptr), Gn, N, _vp(d_y.ptr))
-                pv[nzi], stt[nzi], beta_r[nzi], conv_r[nzi] = run(d_y, nzi)
-            if refitted.any():  # their final LFC was fitted on the replaced counts: so is their reduced model
-                rows = np.nonzero(~keep["naz"])[0]
-                gidx = (keep["rp"] if keep["nzi"] is None else keep["nzi"][keep["rp"]])[rows]
-                if not np.array_equal(np.sort(gidx), np.nonzero(refitted)[0]):
-                    raise RuntimeError("lrt(): the kept replaced counts belong to another result")
-                d_sel = dev(rows.astype(np.int32))
-                d_y2 = DeviceArray(ctx, (len(rows), N), np.int32, ld=self.ldn)
-                held.append(d_y2)
-                ctx.call("dsq_dev_gather_rows_i32", _vp(self._replace_buf.ptr), self.ldn, _vp(d_sel.ptr), len(rows), N,
-                         _vp(d_y2.ptr))
-                pv[gidx], stt[gidx], beta_r[gidx], conv_r[gidx] = run(d_y2, gidx)
-        finally:
-            ctx.sync()
-            for a in held:
-                a.free()
-        z = np.asarray(res.new_all_zeroes, dtype=bool) if res.new_all_zeroes is not None else np.zeros(G, dtype=bool)
-        if z.any():  # ds.py:357-360, dds.py:1380-1383
-            stt[z], pv[z], beta_r[z] = 0.0, 1.0, 0.0
-        return pv, stt, beta_r, conv_r
-
-    # ------------------------------------------------------------------ regularized-log transformation
     def rlog(self, res: DeseqResult, beta_prior_var=None):
-        """Regularized-log transformation (DESeq2's rlog(); csrc/dsq_rlog.h) of the resident counts, post hoc
-        like wald() / lrt(): per gene a ridge-penalised NB GLM with an intercept and one coefficient per sample, fitted at
-        the TREND dispersions ``res.fitted_dispersions`` from the intercept log ``res.normed_means`` with the size factors
-        of ``res`` - a result of ``deseq2()`` or of ``deseq2(stop_after_trend=True)``.  ``beta_prior_var`` (log2 scale):
-        the prior variance of the sample coefficients; None: estimated on the host from all genes with counts
-        (pydeseq2_amd/rlog.py).  One launch.
-        Returns (rlog N x G in log2, intercept, converged, n_iter, beta_prior_var); genes without counts: rlog 0 in every
-        sample, intercept / converged / n_iter NaN."""
-        from .rlog import beta_prior_var as estimate_prior_var
+        """Regularized-log transformation (DESeq2's rlog()) of the resident counts at the trend dispersions
+        of ``res``.  Returns (rlog N x G in log2, intercept, converged, n_iter, beta_prior_var): pydeseq2_amd.rlog.rlog."""
+        from .rlog import rlog
 
-        G, N, ctx = self.G, self.N, self.ctx
-        if res.fitted_dispersions is None:
-            raise ValueError("rlog(): the result carries no fitted_dispersions (run deseq2(), or "
-                             "deseq2(stop_after_trend=True), first).")
-        nz = np.asarray(res.non_zero, dtype=bool)
-        nzi = np.nonzero(nz)[0]
-        Gn = len(nzi)
-        fit = np.asarray(res.fitted_dispersions, dtype=np.float64)[nzi]
-        if not (np.isfinite(fit) & (fit > 0)).all():
-            raise ValueError("rlog(): fitted_dispersions is not a finite positive number on every gene with counts.")
-        if beta_prior_var is not None and not (np.isfinite(beta_prior_var) and beta_prior_var > 0):
-            raise ValueError(f"rlog(): beta_prior_var must be a finite positive number (got {beta_prior_var}).")
-        sf = np.ascontiguousarray(res.size_factors, dtype=np.float64)
-        out = np.zeros((N, G))
-        b0, conv, nit = np.full(G, np.nan), np.full(G, np.nan), np.full(G, np.nan)
-        if Gn == 0:
-            return out, b0, conv, nit, (float(beta_prior_var) if beta_prior_var is not None else np.nan)
-        if beta_prior_var is None:
-            beta_prior_var = estimate_prior_var(self.d_raw.to_host()[:, nzi], sf, fit)
-            if not (np.isfinite(beta_prior_var) and beta_prior_var > 0):
-                raise ValueError(f"rlog(): the estimated beta_prior_var is {beta_prior_var} (no count differs from its "
-                                 "gene's mean, as with a single sample): give beta_prior_var.")
-        beta_prior_var = float(beta_prior_var)
-        held = []
-
-        def dev(a):
-            held.append(DeviceArray.from_host(ctx, np.ascontiguousarray(a)))
-            return held[-1]
-
-        try:
-            d_sf, d_fit = dev(sf), dev(fit)
-            d_bm = dev(np.asarray(res.normed_means, dtype=np.float64)[nzi])
-            if Gn == G:
-                d_y = self.d_y
-            else:
-                d_idx = dev(nzi.astype(np.int32))
-                d_y = DeviceArray(ctx, (Gn, N), np.int32, ld=self.ldn)
-                held.append(d_y)
-                ctx.call("dsq_dev_gather_rows_i32", _vp(self.d_y.ptr), self.ldn, _vp(d_idx.ptr), Gn, N, _vp(d_y.ptr))
-            d_out = DeviceArray(ctx, (Gn, N), np.float64)
-            d_b0, d_cv, d_it = DeviceArray(ctx, (Gn,), np.float64), DeviceArray(ctx, (Gn,), np.uint8), \
-                DeviceArray(ctx, (Gn,), np.int32)
-            held.extend([d_out, d_b0, d_cv, d_it])
-            self._k("rlog", Gn, "dsq_dev_rlog", _vp(d_y.ptr), self.ldn, _vp(d_sf.ptr), N, Gn, _vp(d_fit.ptr), _vp(d_bm.ptr),
-                    c_double(beta_prior_var), _vp(d_out.ptr), _vp(d_b0.ptr), _vp(d_cv.ptr), _vp(d_it.ptr))
-            out[:, nzi] = d_out.to_host().T
-            b0[nzi], conv[nzi], nit[nzi] = d_b0.to_host(), d_cv.to_host(), d_it.to_host()
-        finally:
-            ctx.sync()
-            for a in held:
-                a.free()
-        return out, b0, conv, nit, beta_prior_var
+        return rlog(self, res, beta_prior_var)
 
     # ------------------------------------------------------------------ adaptive shrinkage
     def ash(self, lfc, se):

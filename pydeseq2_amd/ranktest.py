@@ -7,7 +7,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import ALT, _vp
+from ._lib import ALT, DeviceScope, _vp, launch, split
 
 RANK_MAX_L = 16384  # DSQ_RANK_MAX_L: LDS doubles per gene
 RANK_ALT = (None, "greater", "less")
@@ -141,8 +141,6 @@ def ranksum(pipe, d_y, ldn, size_factors, G, labels, strata=None, alt_hypothesis
     pointer ``d_y`` (G rows of pitch ``ldn``) normalised by ``size_factors``, on the device of ``pipe`` (a DeseqPipeline,
     or a ``_lib.Context``): one packed upload, one launch of dsq_dev_ranksum, one download.  ``strata``: one id per
     sample, shared by the comparisons.  Every refusal is raised before anything touches the device."""
-    from ._lib import DeviceArray
-
     check_alternative(alt_hypothesis)
     lab = np.atleast_2d(np.asarray(labels))
     sf = np.ascontiguousarray(size_factors, dtype=np.float64)
@@ -161,29 +159,20 @@ def ranksum(pipe, d_y, ldn, size_factors, G, labels, strata=None, alt_hypothesis
                         P.nstrata.copy(), np.array([q.pairs for q in layouts], np.int64))
     if G == 0:
         return res
-    ctx = getattr(pipe, "ctx", pipe)
     ints = np.concatenate([P.order.ravel(), P.seg.ravel(), P.pad.ravel(), P.nstrata])
     h_in = np.concatenate([sf.view(np.uint8), ints.view(np.uint8), P.labels.ravel().view(np.uint8)])
-    d_in = DeviceArray.from_host(ctx, h_in)
-    d_out = DeviceArray(ctx, (4 * K * G,), np.float64)
-    try:
+    with DeviceScope(split(pipe)[1]) as s:
+        d_in = s.upload(h_in)
+        d_out = s.empty((4 * K * G,), np.float64)
         i0 = d_in.ptr + 8 * N
         o_seg = i0 + 4 * P.order.size
         o_pad = o_seg + 4 * P.seg.size
         o_ns = o_pad + 4 * P.pad.size
         o_lab = o_ns + 4 * K
-        args = (_vp(d_y), int(ldn), _vp(d_in.ptr), N, G, K, _vp(i0), P.ldo, _vp(o_seg), _vp(o_pad), P.lds, _vp(o_ns),
-                _vp(o_lab), P.ldl, ALT[alt_hypothesis], _vp(d_out.ptr), _vp(d_out.ptr + 8 * K * G),
-                _vp(d_out.ptr + 16 * K * G), _vp(d_out.ptr + 24 * K * G), G)
-        if hasattr(pipe, "_k"):
-            pipe._k("ranksum", K * G, "dsq_dev_ranksum", *args)
-        else:
-            ctx.call("dsq_dev_ranksum", *args)
+        launch(pipe, "ranksum", K * G, "dsq_dev_ranksum", _vp(d_y), int(ldn), _vp(d_in.ptr), N, G, K, _vp(i0), P.ldo,
+               _vp(o_seg), _vp(o_pad), P.lds, _vp(o_ns), _vp(o_lab), P.ldl, ALT[alt_hypothesis], _vp(d_out.ptr),
+               _vp(d_out.ptr + 8 * K * G), _vp(d_out.ptr + 16 * K * G), _vp(d_out.ptr + 24 * K * G), G)
         o = d_out.to_host().reshape(4, K, G)
-    finally:
-        ctx.sync()
-        d_in.free()
-        d_out.free()
     res.statistic, res.pvalue, res.usum, res.ties = (o[j].copy() for j in range(4))
     with np.errstate(divide="ignore", invalid="ignore"):  # (no stratum with both groups: no pair, NaN)
         res.auc = res.usum / res.pairs[:, None].astype(np.float64)

@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import pca as _pca
-from ._lib import DSQ_MAX_P, DSQ_PROJ_MAX_Q, GENE_MAJOR, SAMPLE_MAJOR, DeviceArray
+from ._lib import DSQ_MAX_P, DSQ_PROJ_MAX_Q, GENE_MAJOR, SAMPLE_MAJOR, DeviceArray, DeviceScope, launch, split
 
 _vp = C.c_void_p
 U = 2.0 ** -52
@@ -49,16 +49,12 @@ class RuvResult:
 
 
 # ---------------------------------------------------------------------------------------------------------------- inputs
-def _ctx_of(ctx):
-    return ctx, getattr(ctx, "ctx", ctx)
-
-
 class _Counts:
-    """int32 counts on the device, gene-major [G][ld]: a host N x G array is uploaded (transposed), a DeviceArray or a
-    (pointer, ld, N, G) tuple of a pipeline's resident counts is taken as it is."""
+    """int32 counts on the device, gene-major [G][ld]: a host N x G array is uploaded (transposed) into the scope that
+    first asks for its pointer, a DeviceArray or a (pointer, ld, N, G) tuple of a pipeline's resident counts is taken as
+    it is."""
 
-    def __init__(self, ctx, counts):
-        self.own = None
+    def __init__(self, counts):
         if isinstance(counts, tuple):
             self.ptr, self.ld, self.N, self.G = counts
         elif isinstance(counts, DeviceArray):
@@ -78,18 +74,11 @@ class _Counts:
             self.ptr, self.ld = None, self.N
         if self.N < 1:
             raise ValueError("at least one sample is needed.")
-        self.ctx = ctx
 
-    def pointer(self):
+    def pointer(self, s):
         if self.ptr is None:
-            self.own = DeviceArray.from_host(self.ctx, self.host) if self.G else None
-            self.ptr = self.own.ptr if self.own is not None else 0
+            self.ptr = s.upload(self.host).ptr if self.G else 0
         return self.ptr
-
-    def free(self):
-        if self.own is not None:
-            self.own.free()
-            self.own = None
 
 
 def _size_factors(sf, N, needed=True):
@@ -119,7 +108,7 @@ def check_q(q):
 def project_plan(ctx, N):
     """(waves per workgroup, where a row stays between the passes - 2 registers, 1 LDS, 0 nowhere -, dynamic LDS bytes) of
     the projection of rows of N doubles."""
-    _, ctx = _ctx_of(ctx)
+    ctx = split(ctx)[1]
     w, s, b = C.c_int(), C.c_int(), C.c_size_t()
     if ctx.lib.dsq_project_plan(int(N), C.byref(w), C.byref(s), C.byref(b)) != 0:
         raise ValueError(f"project_plan: at least one sample is needed (got N = {N}).")
@@ -127,18 +116,13 @@ def project_plan(ctx, N):
 
 
 # ------------------------------------------------------------------------------------------------------- device stages
-def _dev_log_counts(pipe, ctx, cnt, sf, normalized, eps):
-    """-> DeviceArray [G][N] float64 (the caller frees it)"""
-    d_out = DeviceArray(ctx, (cnt.G, cnt.N), np.float64)
-    d_sf = DeviceArray.from_host(ctx, sf) if sf is not None else None
-    try:
-        _pca._call(pipe, "log_counts", cnt.G, "dsq_dev_log_counts", _vp(cnt.pointer()), cnt.ld,
-                   _vp(d_sf.ptr) if d_sf is not None else None, cnt.N, cnt.G, int(bool(normalized)), C.c_double(eps),
-                   _vp(d_out.ptr), cnt.N)
-    finally:
-        ctx.sync()
-        if d_sf is not None:
-            d_sf.free()
+def _dev_log_counts(who, s, cnt, sf, normalized, eps):
+    """-> DeviceArray [G][N] float64 of the scope s"""
+    d_out = s.empty((cnt.G, cnt.N), np.float64)
+    d_sf = s.upload(sf) if sf is not None else None
+    launch(who, "log_counts", cnt.G, "dsq_dev_log_counts", _vp(cnt.pointer(s)), cnt.ld,
+           _vp(d_sf.ptr) if d_sf is not None else None, cnt.N, cnt.G, int(bool(normalized)), C.c_double(eps),
+           _vp(d_out.ptr), cnt.N)
     return d_out
 
 
@@ -153,20 +137,13 @@ def _check_fit(N, G, design, beta, dispersions):
     return np.ascontiguousarray(X.T), beta, disp
 
 
-def _dev_residuals(pipe, ctx, cnt, sf, Xt, beta, disp, kind):
-    """-> DeviceArray [G][N] float64 (the caller frees it)"""
-    d_out = DeviceArray(ctx, (cnt.G, cnt.N), np.float64)
-    held = [DeviceArray.from_host(ctx, a) for a in (sf, Xt, beta, disp)] if cnt.G else []
-    try:
-        if cnt.G:
-            d_sf, d_Xt, d_b, d_d = held
-            _pca._call(pipe, "nb_residuals", cnt.G, "dsq_dev_nb_residuals", _vp(cnt.pointer()), cnt.ld, _vp(d_sf.ptr),
-                       _vp(d_Xt.ptr), cnt.N, Xt.shape[0], cnt.N, cnt.G, _vp(d_d.ptr), _vp(d_b.ptr), kind, _vp(d_out.ptr),
-                       cnt.N)
-    finally:
-        ctx.sync()
-        for a in held:
-            a.free()
+def _dev_residuals(who, s, cnt, sf, Xt, beta, disp, kind):
+    """-> DeviceArray [G][N] float64 of the scope s"""
+    d_out = s.empty((cnt.G, cnt.N), np.float64)
+    if cnt.G:
+        d_sf, d_Xt, d_b, d_d = (s.upload(a) for a in (sf, Xt, beta, disp))
+        launch(who, "nb_residuals", cnt.G, "dsq_dev_nb_residuals", _vp(cnt.pointer(s)), cnt.ld, _vp(d_sf.ptr),
+               _vp(d_Xt.ptr), cnt.N, Xt.shape[0], cnt.N, cnt.G, _vp(d_d.ptr), _vp(d_b.ptr), kind, _vp(d_out.ptr), cnt.N)
     return d_out
 
 
@@ -179,72 +156,54 @@ def _check_PB(P, B, N):
     return np.ascontiguousarray(P.T), np.ascontiguousarray(B.T)
 
 
-def _dev_project(pipe, ctx, d_x, ld, N, G, Pt, Bt, post, eps, d_out, ldo, want_coef):
+def _dev_project(who, s, d_x, ld, N, G, Pt, Bt, post, eps, d_out, ldo, want_coef):
     """out = x - (x P) B^T on gene-major device rows; d_out may be d_x.  -> the G x q coefficients on the host, or None"""
     q = Pt.shape[0]
-    d_Pt, d_Bt = DeviceArray.from_host(ctx, Pt), DeviceArray.from_host(ctx, Bt)
-    d_c = DeviceArray(ctx, (G, q), np.float64) if want_coef and G else None
-    try:
-        _pca._call(pipe, "project_out", G, "dsq_dev_project_out", _vp(d_x), ld, _vp(d_Pt.ptr), _vp(d_Bt.ptr), N, q, N, G,
-                   post, C.c_double(eps), _vp(d_out), ldo, _vp(d_c.ptr) if d_c is not None else None)
-        coef = d_c.to_host() if d_c is not None else (np.zeros((0, q)) if want_coef else None)
-    finally:
-        ctx.sync()
-        for a in (d_Pt, d_Bt, d_c):
-            if a is not None:
-                a.free()
-    return coef
+    d_Pt, d_Bt = s.upload(Pt), s.upload(Bt)
+    d_c = s.empty((G, q), np.float64) if want_coef and G else None
+    launch(who, "project_out", G, "dsq_dev_project_out", _vp(d_x), ld, _vp(d_Pt.ptr), _vp(d_Bt.ptr), N, q, N, G,
+           post, C.c_double(eps), _vp(d_out), ldo, _vp(d_c.ptr) if d_c is not None else None)
+    return d_c.to_host() if d_c is not None else (np.zeros((0, q)) if want_coef else None)
 
 
 class _GeneMajor:
     """A float64 matrix as gene-major device rows: a host N x G array is uploaded and transposed on the device
     (dsq_dev_f64_to_gene_major), a sample-major DeviceArray is transposed into a copy, a gene-major one is taken as it is."""
 
-    def __init__(self, pipe, ctx, x, layout):
-        R = _pca._Resident(ctx, x, layout)
-        self.N, self.G, self.own = R.N, R.G, None
+    def __init__(self, x, layout):
+        R = _pca._Resident(x, layout)
+        self.N, self.G = R.N, R.G
         if self.N < 1:
             raise ValueError("at least one sample is needed.")
-        self._R, self._pipe, self._ctx = R, pipe, ctx
+        self._R = R
 
-    def pointer(self):
-        """(pointer, pitch) of the rows; call once, after every refusal"""
-        R, ctx = self._R, self._ctx
+    def pointer(self, s):
+        """(pointer, pitch) of the rows, which the scope s owns unless they are the caller's; call once, after every
+        refusal"""
+        R = self._R
         if R.layout == GENE_MAJOR:
-            return R.ptr(ctx), R.ld
-        self.own = DeviceArray(ctx, (self.G, self.N), np.float64)
+            return R.ptr(s), R.ld
+        d_gm = s.empty((self.G, self.N), np.float64)
         if self.G:
             if R.ld != self.G:
                 raise ValueError("a sample-major DeviceArray must be contiguous (ld == G).")
-            ctx.call("dsq_dev_f64_to_gene_major", _vp(R.ptr(ctx)), SAMPLE_MAJOR, self.N, self.G, _vp(self.own.ptr), self.N)
-            ctx.sync()
-        R.free()
-        return self.own.ptr, self.N
-
-    def free(self):
-        self._R.free()
-        if self.own is not None:
-            self.own.free()
-            self.own = None
+            with DeviceScope(s.ctx) as t:  # (an uploaded sample-major copy lives until the transposition has run)
+                s.ctx.call("dsq_dev_f64_to_gene_major", _vp(R.ptr(t)), SAMPLE_MAJOR, self.N, self.G, _vp(d_gm.ptr),
+                           self.N)
+        return d_gm.ptr, self.N
 
 
 # ------------------------------------------------------------------------------------------------------- public stages
 def log_counts(ctx, counts, size_factors=None, normalized=True, epsilon=1.0):
     """``log(y / sf + epsilon)`` (``normalized=False``: ``log(y + epsilon)``) of ``counts`` - a host N x G array of
     non-negative integers or an int32 ``DeviceArray`` G x N - as a host N x G array."""
-    pipe, ctx = _ctx_of(ctx)
     eps = _check_eps(epsilon)
-    cnt = _Counts(ctx, counts)
+    cnt = _Counts(counts)
     sf = _size_factors(size_factors, cnt.N, normalized)
     if cnt.G == 0:
         return np.zeros((cnt.N, 0))
-    try:
-        d = _dev_log_counts(pipe, ctx, cnt, sf if normalized else None, normalized, eps)
-        out = d.to_host().T
-        d.free()
-    finally:
-        ctx.sync()
-        cnt.free()
+    with DeviceScope(split(ctx)[1]) as s:
+        out = _dev_log_counts(ctx, s, cnt, sf if normalized else None, normalized, eps).to_host().T
     return np.ascontiguousarray(out)
 
 
@@ -252,21 +211,15 @@ def nb_residuals(ctx, counts, size_factors, design, beta, dispersions, kind="dev
     """Residuals of the NB GLM of a finished fit, N x G: ``mu = sf exp(design @ beta_g)`` (``beta`` G x P, natural log),
     ``kind="deviance"``: sign(y - mu) sqrt(D), ``"pearson"``: (y - mu) / sqrt(mu + alpha mu^2).  A gene without counts, or
     with a NaN coefficient or dispersion: NaN."""
-    pipe, ctx = _ctx_of(ctx)
     if kind not in KIND:
         raise ValueError(f"kind must be 'deviance' or 'pearson' (got {kind!r}).")
-    cnt = _Counts(ctx, counts)
+    cnt = _Counts(counts)
     sf = _size_factors(size_factors, cnt.N)
     Xt, beta, disp = _check_fit(cnt.N, cnt.G, design, beta, dispersions)
     if cnt.G == 0:
         return np.zeros((cnt.N, 0))
-    try:
-        d = _dev_residuals(pipe, ctx, cnt, sf, Xt, beta, disp, KIND[kind])
-        out = d.to_host().T
-        d.free()
-    finally:
-        ctx.sync()
-        cnt.free()
+    with DeviceScope(split(ctx)[1]) as s:
+        out = _dev_residuals(ctx, s, cnt, sf, Xt, beta, disp, KIND[kind]).to_host().T
     return np.ascontiguousarray(out)
 
 
@@ -275,28 +228,23 @@ def project_out(ctx, x, P, B, post=None, epsilon=1.0, layout=SAMPLE_MAJOR, retur
     matrices, q <= 64; ``post``: None, "exp" (``exp(.) - epsilon``) or "round" (``max(rint(exp(.) - epsilon), 0)``).
     Returns the N x G result (with ``return_coef``: and the G x q coefficients ``x P``).  ``inplace`` (a gene-major
     ``DeviceArray`` only): the rows are overwritten on the device and nothing but the coefficients is returned."""
-    pipe, ctx = _ctx_of(ctx)
     if post not in POST:
         raise ValueError(f"post must be None, 'exp' or 'round' (got {post!r}).")
     eps = _check_eps(epsilon)
     if inplace and not (isinstance(x, DeviceArray) and layout == GENE_MAJOR):
         raise ValueError("inplace: a gene-major DeviceArray only.")
-    M = _GeneMajor(pipe, ctx, x, layout)
+    M = _GeneMajor(x, layout)
     Pt, Bt = _check_PB(P, B, M.N)
     if M.G == 0:  # (nothing to launch, as log_counts and nb_residuals)
         coef = np.zeros((0, Pt.shape[0])) if return_coef else None
         return coef if inplace else ((np.zeros((M.N, 0)), coef) if return_coef else np.zeros((M.N, 0)))
-    try:
-        ptr, ld = M.pointer()
+    with DeviceScope(split(ctx)[1]) as s:
+        ptr, ld = M.pointer(s)
         if inplace:
-            return _dev_project(pipe, ctx, ptr, ld, M.N, M.G, Pt, Bt, POST[post], eps, ptr, ld, return_coef)
-        d_out = DeviceArray(ctx, (M.G, M.N), np.float64)
-        coef = _dev_project(pipe, ctx, ptr, ld, M.N, M.G, Pt, Bt, POST[post], eps, d_out.ptr, M.N, return_coef)
+            return _dev_project(ctx, s, ptr, ld, M.N, M.G, Pt, Bt, POST[post], eps, ptr, ld, return_coef)
+        d_out = s.empty((M.G, M.N), np.float64)
+        coef = _dev_project(ctx, s, ptr, ld, M.N, M.G, Pt, Bt, POST[post], eps, d_out.ptr, M.N, return_coef)
         out = np.ascontiguousarray(d_out.to_host().T)
-        d_out.free()
-    finally:
-        ctx.sync()
-        M.free()
     return (out, coef) if return_coef else out
 
 
@@ -362,9 +310,8 @@ def ruv(ctx, counts, size_factors, k, controls=None, method="g", normalized=True
     residuals of ``fit = (design, beta, dispersions[, has_counts])``, by default over all genes with counts - and the coefficients of
     ALL genes on them.  ``return_counts``: the normalised counts (``round=False``: unrounded); ``corrected``: Y' itself.
     Returns a RuvResult.  ValueError: see check_ruv_args; fewer resolved factors than ``drop`` + 1."""
-    pipe, ctx = _ctx_of(ctx)
     eps = _check_eps(epsilon)
-    cnt = _Counts(ctx, counts)
+    cnt = _Counts(counts)
     N, G = cnt.N, cnt.G
     sf = _size_factors(size_factors, N, normalized or method == "r")
     has = None
@@ -376,14 +323,11 @@ def ruv(ctx, counts, size_factors, k, controls=None, method="g", normalized=True
         if has is None and not isinstance(counts, (tuple, DeviceArray)):
             has = (cnt.host != 0).any(axis=1)
     sel = check_ruv_args(N, G, k, controls, drop, method, has)
-    d_Y = d_R = d_S = None
-    try:
-        d_Y = _dev_log_counts(pipe, ctx, cnt, sf if normalized else None, normalized, eps)
-        if method == "r":
-            d_R = _dev_residuals(pipe, ctx, cnt, sf, Xt, beta, disp, 0)
-        R = _pca._Resident(ctx, d_R if d_R is not None else d_Y, GENE_MAJOR)
-        d_S = _pca._gram_on_device(pipe, ctx, R, sel, center)
-        S = d_S.to_host()
+    with DeviceScope(split(ctx)[1]) as s:
+        d_Y = _dev_log_counts(ctx, s, cnt, sf if normalized else None, normalized, eps)
+        d_R = _dev_residuals(ctx, s, cnt, sf, Xt, beta, disp, 0) if method == "r" else None
+        R = _pca._Resident(d_R if d_R is not None else d_Y, GENE_MAJOR)
+        S = _pca._gram_on_device(ctx, s, R, sel, center).to_host()
         if not np.isfinite(S).all():
             raise ValueError("ruv(): the Gram of the control genes is not finite (a control gene without a fit?).")
         W, d, k_eff = factors_from_gram(S, k, len(sel), drop)
@@ -394,21 +338,14 @@ def ruv(ctx, counts, size_factors, k, controls=None, method="g", normalized=True
         out = RuvResult(W, d, k_eff, None, sel)
         coef = None
         if return_counts:
-            d_o = DeviceArray(ctx, (G, N), np.float64)
-            coef = _dev_project(pipe, ctx, d_Y.ptr, N, N, G, Pt, Bt, 2 if round else 1, eps, d_o.ptr, N, True)
+            d_o = s.empty((G, N), np.float64)
+            coef = _dev_project(ctx, s, d_Y.ptr, N, N, G, Pt, Bt, 2 if round else 1, eps, d_o.ptr, N, True)
             out.normalized_counts = np.ascontiguousarray(d_o.to_host().T)
-            d_o.free()
         if corrected or coef is None:  # (in place: the log counts are not needed again)
-            coef = _dev_project(pipe, ctx, d_Y.ptr, N, N, G, Pt, Bt, 0, eps, d_Y.ptr, N, True)
+            coef = _dev_project(ctx, s, d_Y.ptr, N, N, G, Pt, Bt, 0, eps, d_Y.ptr, N, True)
             if corrected:
                 out.corrected = np.ascontiguousarray(d_Y.to_host().T)
         out.alpha = np.ascontiguousarray(coef.T)
-    finally:
-        ctx.sync()
-        for a in (d_Y, d_R, d_S):
-            if a is not None:
-                a.free()
-        cnt.free()
     return out
 
 
@@ -477,20 +414,14 @@ def batch_projection(D, Xb):
 def remove_batch_effect(ctx, x, batch=None, batch2=None, covariates=None, design=None, layout=SAMPLE_MAJOR):
     """limma's ``removeBatchEffect`` of an N x G matrix (host array, or a DeviceArray in ``layout``): per gene the least
     squares fit of [design | batch terms], and the fitted batch terms subtracted.  See batch_design.  -> N x G."""
-    pipe, ctx = _ctx_of(ctx)
-    M = _GeneMajor(pipe, ctx, x, layout)
+    M = _GeneMajor(x, layout)
     D, Xb, _ = batch_design(M.N, batch, batch2, covariates, design)
     P, B = batch_projection(D, Xb)
     Pt, Bt = _check_PB(P, B, M.N)
     if M.G == 0:
         return np.zeros((M.N, 0))
-    try:
-        ptr, ld = M.pointer()
-        d_out = DeviceArray(ctx, (M.G, M.N), np.float64)
-        _dev_project(pipe, ctx, ptr, ld, M.N, M.G, Pt, Bt, 0, 1.0, d_out.ptr, M.N, False)
-        out = np.ascontiguousarray(d_out.to_host().T)
-        d_out.free()
-    finally:
-        ctx.sync()
-        M.free()
-    return out
+    with DeviceScope(split(ctx)[1]) as s:
+        ptr, ld = M.pointer(s)
+        d_out = s.empty((M.G, M.N), np.float64)
+        _dev_project(ctx, s, ptr, ld, M.N, M.G, Pt, Bt, 0, 1.0, d_out.ptr, M.N, False)
+        return np.ascontiguousarray(d_out.to_host().T)

@@ -18,7 +18,7 @@ import numpy as np
 sys.path.insert(0, ".")
 from pydeseq2_amd import pca as _pca  # noqa: E402
 from pydeseq2_amd import ruv  # noqa: E402
-from pydeseq2_amd._lib import GENE_MAJOR, Context, DeviceArray, _vp  # noqa: E402
+from pydeseq2_amd._lib import GENE_MAJOR, Context, DeviceArray, DeviceScope, _vp  # noqa: E402
 
 
 def stats(v):
@@ -100,10 +100,11 @@ def main():
         dev[name]["GBps"] = 16.0 * N * G / dev[name]["median"] / 1e6
         show(f"dsq_dev_project_out (q = {k}, post {post})", dev[name], f"  {dev[name]['GBps']:.0f} GB/s of 16 N G bytes")
     for name, sel in (("gram_controls_g", ctl), ("gram_all_genes", None)):
-        R = _pca._Resident(ctx, d_Y, GENE_MAJOR)
+        R = _pca._Resident(d_Y, GENE_MAJOR)
 
         def gram():
-            _pca._gram_on_device(ctx, ctx, R, sel, True).free()
+            with DeviceScope(ctx) as s:
+                _pca._gram_on_device(ctx, s, R, sel, True)
 
         out["wall_ms"][name] = wall(a.reps, gram)
         show(f"centred Gram, {len(sel) if sel is not None else G} genes (row means + dsq_dev_sample_gram, wall)", out["wall_ms"][name])
