@@ -493,6 +493,24 @@ int dsq_dev_lrt(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, c
 /* d_out[i] = survival function of the chi-square distribution with df degrees of freedom (an integer, 1 ... 127) at
  * d_x[i] (scipy.stats.chi2.sf): 1 for x <= 0. */
 int dsq_dev_chisq_sf(dsq_ctx* ctx, const double* d_x, int n, int df, double* d_out);
+/* Quasi-likelihood F-test (edgeR's glmQLFit / glmQLFTest; csrc/dsq_ql.h), step 1: from the coefficients of
+ * a full and a nested reduced fit at ONE dispersion per gene (d_disp: the trend) per gene
+ *   d_num = D_reduced - D_full (the statistic of dsq_dev_lrt, never a difference of two deviances),
+ *   d_dev = D_full = sum_n d(y, mu),  d = 2 [y log(y / mu) - (y + r) log((y + r) / (mu + r))],  2 r log1p(mu / r) at y = 0,
+ *   d_s2  = D_full / (N - P),   r = 1 / disp,  mu = sf exp(X beta).
+ * Arguments as dsq_dev_lrt.  N <= P (no residual degrees of freedom): d_num and d_dev as above, d_s2 is the plain quotient
+ * by N - P (infinite, NaN or negative) and means nothing - pydeseq2_amd.ql refuses such a design before it gets here. */
+int dsq_dev_ql_deviance(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, const double* d_Xt, int ldx, int P,
+                        const double* d_Xt_reduced, int ldx_reduced, int P_reduced, int N, int G, const double* d_disp,
+                        const double* d_beta, const double* d_beta_reduced, double* d_num, double* d_dev, double* d_s2);
+/* Step 2, elementwise: d_F[i] = max(d_num[i], 0) / (df_test d_s2_post[i]) and its p-value on (df_test, df_total) degrees of
+ * freedom; df_total = infinity: the chi-square limit dsq_dev_chisq_sf(df_test F, df_test) - what the caller passes when its
+ * moderation ended with infinite prior degrees of freedom (pydeseq2_amd.ql.score_df).  df_test: 1 ... 127. */
+int dsq_dev_ql_score(dsq_ctx* ctx, const double* d_num, const double* d_s2_post, int n, int df_test, double df_total,
+                     double* d_F, double* d_pvals);
+/* d_out[i] = survival function of the F distribution with d1 (an integer, 1 ... 127) and d2 (real, finite, > 0)
+ * degrees of freedom at d_F[i] (scipy.stats.f.sf): 1 for F <= 0, NaN for NaN. */
+int dsq_dev_f_sf(dsq_ctx* ctx, const double* d_F, int n, int d1, double d2, double* d_out);
 /* Regularized-log transformation (DESeq2's rlog(); csrc/dsq_rlog.h): per gene the ridge-penalised NB GLM with an
  * intercept and one coefficient per sample (penalty 1 / beta_prior_var on the log2 scale, 1e-6 on the intercept), fitted by
  * IRLS from the intercept ln d_base_mean[g] at the TREND dispersion d_disp_fit[g] (deviance criterion 1e-4, at most 100

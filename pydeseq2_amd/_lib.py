@@ -212,6 +212,10 @@ def load():
           c_double, c_int, _vp, _vp, _vp)
     proto("dsq_dev_lrt", _vp, _vp, c_int, _vp, _vp, c_int, c_int, _vp, c_int, c_int, c_int, c_int, _vp, _vp, _vp, _vp, _vp)
     proto("dsq_dev_chisq_sf", _vp, _vp, c_int, c_int, _vp)
+    proto("dsq_dev_ql_deviance", _vp, _vp, c_int, _vp, _vp, c_int, c_int, _vp, c_int, c_int, c_int, c_int, _vp, _vp, _vp,
+          _vp, _vp, _vp)
+    proto("dsq_dev_ql_score", _vp, _vp, _vp, c_int, c_int, c_double, _vp, _vp)
+    proto("dsq_dev_f_sf", _vp, _vp, c_int, c_int, c_double, _vp)
     proto("dsq_dev_rlog", _vp, _vp, c_int, _vp, c_int, c_int, _vp, _vp, c_double, _vp, _vp, _vp, _vp)
     proto("dsq_dev_ash", _vp, _vp, _vp, c_int, c_int, c_int, _vp, _vp, c_int, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
     proto("dsq_ranksum_plan", c_int, C.POINTER(c_int), C.POINTER(c_size_t))
@@ -266,6 +270,7 @@ EXPORTS = [
     "dsq_dev_row_meanvar", "dsq_sample_gram_work_doubles", "dsq_dev_sample_gram", "dsq_dev_gram_dist",
     "dsq_ranksum_plan", "dsq_dev_ranksum",
     "dsq_dev_log_counts", "dsq_dev_nb_residuals", "dsq_project_plan", "dsq_dev_project_out",
+    "dsq_dev_ql_deviance", "dsq_dev_ql_score", "dsq_dev_f_sf",
 ]
 
 

@@ -17,6 +17,7 @@ import warnings
 import numpy as np
 import pandas as pd
 
+from . import ql as _ql
 from . import ranktest as _ranktest
 from . import summary as _summary
 from ._design import DesignPack
@@ -991,6 +992,12 @@ def _check_lrt_hypothesis(lfc_null, alt_hypothesis):
                          "(use test='wald' for a thresholded or one-sided test).")
 
 
+def _check_ql_hypothesis(lfc_null, alt_hypothesis):
+    if lfc_null != 0 or alt_hypothesis is not None:
+        raise ValueError("The quasi-likelihood F-test has no lfc_null / alt_hypothesis: it compares two nested designs "
+                         "(use test='wald' for a thresholded or one-sided test).")
+
+
 def reduced_design_matrix(dds, reduced) -> pd.DataFrame:
     """The reduced design of a likelihood-ratio test as a DataFrame over the samples of ``dds``: a formula over its
     metadata (built like the full design, same ``ref_level``), a DataFrame or a matrix.  Host only.  ValueError when it
@@ -1034,13 +1041,25 @@ class DeseqStats:
     "greater" or "less".  ``summary()`` keeps ``baseMean``, ``log2FoldChange`` and ``lfcSE`` of the GLM fit, passes the rank
     test's p-values through independent filtering and BH and adds ``auc``; the Cook's filter is NOT applied: an outlying
     count moves a rank by at most one group size, which is what the test is robust against.  Single process only, like
-    ``test="LRT"``: the distributed pipeline has no rank-sum launch."""
+    ``test="LRT"``: the distributed pipeline has no rank-sum launch.
+
+    ``test="QL"`` replaces them by the quasi-likelihood F-test (edgeR's ``glmQLFit`` / ``glmQLFTest``, what DESeq2 reaches
+    through ``fitType="glmGamPoi"``) - the parametric test for a large cohort, where the Wald and
+    likelihood-ratio p-values are anti-conservative: the NB dispersion is fixed at the trend, a per-gene quasi-likelihood
+    dispersion (residual deviance / (N - P), moderated across genes like limma's ``squeezeVar``) absorbs the gene-specific
+    variability, and an F-test with finite denominator degrees of freedom replaces the chi-square test.  Without
+    ``reduced=`` it tests the contrast (any contrast: one numerator degree of freedom), with ``reduced="~batch"`` the
+    nested model, as ``test="LRT"`` does.  ``summary()`` keeps ``log2FoldChange`` / ``lfcSE`` of the contrast, puts F in
+    ``stat``, passes the p-values through the Cook's filter, independent filtering and BH, and adds ``ql_dispersion``;
+    ``ql_df0`` / ``ql_s02`` hold the prior.  No ``lfc_null`` / ``alt_hypothesis``; needs N - P >= 1 and a fit with trend
+    dispersions.  Single process only."""
 
     def __init__(self, dds: DeseqDataSet, contrast, alpha=0.05, cooks_filter=True, independent_filter=True,
                  prior_LFC_var=None, lfc_null=0.0, alt_hypothesis=None, inference=None, quiet=True, n_cpus=None, *,
                  test="wald", reduced=None, strata=None):
-        if test not in ("wald", "LRT", "wilcoxon"):
-            raise ValueError(f"test must be 'wald' or 'LRT', or 'wilcoxon' for the rank-sum test (got {test!r}).")
+        if test not in ("wald", "LRT", "wilcoxon", "QL"):
+            raise ValueError(f"test must be 'wald' or 'LRT', or 'wilcoxon' for the rank-sum test, or 'QL' for the "
+                             f"quasi-likelihood F-test (got {test!r}).")
         self.test, self.reduced_design, self.strata = test, None, None
         if test == "wilcoxon":  # (host-only checks: before anything touches the GPU)
             _ranktest.check_alternative(alt_hypothesis, lfc_null)
@@ -1059,8 +1078,14 @@ class DeseqStats:
                 raise ValueError("test='LRT' needs a reduced design: reduced='~batch', '~1', a matrix or a DataFrame.")
             _check_lrt_hypothesis(lfc_null, alt_hypothesis)
             self.reduced_design = reduced_design_matrix(dds, reduced)
+        elif test == "QL":  # (host-only checks: before anything touches the GPU)
+            _check_ql_hypothesis(lfc_null, alt_hypothesis)
+            _ql.check_residual_df(*dds.obsm["design_matrix"].shape)
+            if reduced is not None:
+                self.reduced_design = reduced_design_matrix(dds, reduced)
         elif reduced is not None:
-            raise ValueError("reduced is the reduced design of the likelihood-ratio test: pass test='LRT' with it.")
+            raise ValueError("reduced is the reduced design of the likelihood-ratio test (test='LRT') or of the "
+                             "quasi-likelihood F-test (test='QL'): pass one of them with it.")
         finish = getattr(dds, "_ensure_finished", None)
         if finish is not None:
             finish()  # (a stage-wise pass left open after fit_LFC() / calculate_cooks() is run to its end)
@@ -1080,6 +1105,11 @@ class DeseqStats:
         self.shrunk_LFCs = False
         if test == "wilcoxon":
             self._rank_layout()
+        if test == "QL":
+            if self.reduced_design is None:  # the contrast itself: X restricted to the null space of the contrast
+                Xr = _ql.null_space_reduced(self.design_matrix.to_numpy(dtype=float), self.contrast_vector)
+                self.reduced_design = pd.DataFrame(Xr, index=dds.obs_names, columns=[f"n{j}" for j in range(Xr.shape[1])])
+            _ql.check_ql_inputs(*self.design_matrix.shape, dds._res.fitted_dispersions, dds._res.non_zero)
 
     def _rank_layout(self):
         """Labels (1 tested, 0 reference, -1 left out) and stratum ids of the rank-sum test, from ``obs``: host only."""
@@ -1144,6 +1174,9 @@ class DeseqStats:
         ``alt_hypothesis``): every contrast a ``[factor, tested, ref]`` list; the rank-sum tests of all of them run in
         one launch (``DeseqPipeline.ranksum``) after the Wald launch that gives ``lfcSE``.  Single process only: the
         distributed pipeline has no multi-contrast launch."""
+        if kwargs.get("test", "wald") == "QL":
+            raise ValueError("DeseqStats.batch() runs Wald tests: test='QL' fits a reduced design per contrast (use "
+                             "DeseqStats(dds, contrast, test='QL') for each).")
         if kwargs.get("test", "wald") not in ("wald", "wilcoxon") or kwargs.get("reduced") is not None:
             raise ValueError("DeseqStats.batch() runs Wald tests: the likelihood-ratio statistic does not depend on the "
                              "contrast (use DeseqStats(dds, contrast, test='LRT', reduced=...) once).")
@@ -1194,6 +1227,30 @@ class DeseqStats:
         if hasattr(self, "padj"):
             del self.padj
 
+    def run_ql_test(self):
+        """Quasi-likelihood F-test (``DeseqPipeline.ql``) of the contrast - or of ``reduced`` when one was given:
+        ``statistics`` (F) and ``p_values`` are the test's, ``SE`` stays the contrast's standard error (a Wald quantity);
+        also ``ql_dispersion`` (the moderated quasi-likelihood dispersion s2_post), ``ql_dispersion_raw`` (deviance /
+        (N - P)), ``ql_df0`` / ``ql_s02`` (the prior), ``ql_df_total``, ``ql_LFC`` / ``reduced_LFC`` (both fits at the
+        trend dispersion) and their ``ql_converged`` / ``reduced_converged`` flags."""
+        if self.test != "QL":
+            raise ValueError("run_ql_test() needs DeseqStats(..., test='QL').")
+        _check_ql_hypothesis(self.lfc_null, self.alt_hypothesis)
+        if not hasattr(self, "SE"):
+            self.run_wald_test()
+        r = self.dds._pipe.ql(self.dds._res, self.reduced_design.to_numpy())
+        idx = self.dds.var_names
+        self.p_values, self.statistics = pd.Series(r.pvalue, index=idx), pd.Series(r.F, index=idx)
+        self.ql_dispersion, self.ql_dispersion_raw = pd.Series(r.s2_post, index=idx), pd.Series(r.s2, index=idx)
+        self.ql_df0, self.ql_s02, self.ql_df_total = float(r.df0), float(r.s02), float(r.df_total)
+        self.ql_LFC = pd.DataFrame(r.LFC, index=idx, columns=self.LFC.columns)
+        self.reduced_LFC = pd.DataFrame(r.reduced_LFC, index=idx, columns=self.reduced_design.columns)
+        self.ql_converged = pd.Series(r.converged, index=idx)
+        self.reduced_converged = pd.Series(r.reduced_converged, index=idx)
+        self._wald_key = ("QL",)
+        if hasattr(self, "padj"):
+            del self.padj
+
     def run_ranksum_test(self):
         """Wilcoxon rank-sum test of the contrast's two levels (``DeseqPipeline.ranksum``): ``statistics`` (the z
         statistic), ``p_values`` and ``auc`` (the probability that a tested sample lies above a reference sample of its
@@ -1232,10 +1289,14 @@ class DeseqStats:
         The Wald test is (re)run only when there are no p-values yet or ``lfc_null`` / ``alt_hypothesis`` change
         (ds.py:255-264), so a summary after ``lfc_shrink`` keeps the shrunk coefficients with their standard errors.
         With ``test="LRT"`` the statistic and the p-values are the likelihood-ratio test's; with ``test="wilcoxon"``
-        the rank-sum test's, without the Cook's filter (the test is rank-based) and with an ``auc`` column."""
+        the rank-sum test's, without the Cook's filter (the test is rank-based) and with an ``auc`` column; with
+        ``test="QL"`` the quasi-likelihood F statistic and its p-values, with a ``ql_dispersion`` column."""
         if self.test == "wilcoxon":  # (refused before the object changes)
             _ranktest.check_alternative(kwargs.get("alt_hypothesis", self.alt_hypothesis),
                                         kwargs.get("lfc_null", self.lfc_null))
+        if self.test in ("LRT", "QL"):
+            (_check_lrt_hypothesis if self.test == "LRT" else _check_ql_hypothesis)(
+                kwargs.get("lfc_null", self.lfc_null), kwargs.get("alt_hypothesis", self.alt_hypothesis))
         self.lfc_null = kwargs.get("lfc_null", self.lfc_null)
         self.alt_hypothesis = kwargs.get("alt_hypothesis", self.alt_hypothesis)
         if self.test == "LRT":
@@ -1245,6 +1306,10 @@ class DeseqStats:
         elif self.test == "wilcoxon":
             if getattr(self, "_wald_key", None) != ("wilcoxon", self.alt_hypothesis):
                 self.run_ranksum_test()
+        elif self.test == "QL":
+            _check_ql_hypothesis(self.lfc_null, self.alt_hypothesis)
+            if getattr(self, "_wald_key", None) != ("QL",):
+                self.run_ql_test()
         elif not hasattr(self, "p_values") or getattr(self, "_wald_key", None) != (self.lfc_null, self.alt_hypothesis):
             self.run_wald_test()
         if not hasattr(self, "padj"):
@@ -1263,6 +1328,8 @@ class DeseqStats:
         df["stat"], df["pvalue"], df["padj"] = self.statistics, self.p_values, self.padj
         if self.test == "wilcoxon":
             df["auc"] = self.auc
+        if self.test == "QL":
+            df["ql_dispersion"] = self.ql_dispersion
         if getattr(self, "_ash_svalue", False):
             df["svalue"] = self.svalues
         self.results_df = df
@@ -1390,8 +1457,8 @@ class DeseqStats:
             o._drop_ash()
             if not hasattr(o, "SE"):
                 o.run_wald_test()
-                if o.test == "LRT":
-                    del o._wald_key  # (summary() still owes the likelihood-ratio statistic)
+                if o.test in ("LRT", "QL"):
+                    del o._wald_key  # (summary() still owes the likelihood-ratio / quasi-likelihood statistic)
         lfc = np.stack([o.LFC.to_numpy() @ o.contrast_vector for o in stats])
         se = np.stack([o.SE.to_numpy() for o in stats])
         res = dds._pipe.ash(lfc, se)

@@ -630,6 +630,37 @@ int dsq_dev_chisq_sf(dsq_ctx* ctx, const double* d_x, int n, int df, double* d_o
     return DSQ_OK;
 }
 
+int dsq_dev_ql_deviance(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, const double* d_Xt, int ldx, int P,
+                        const double* d_Xt_reduced, int ldx_reduced, int P_reduced, int N, int G, const double* d_disp,
+                        const double* d_beta, const double* d_beta_reduced, double* d_num, double* d_dev, double* d_s2) {
+    DSQ_CHECK_ARG(P >= 2 && P <= DSQ_MAX_P, "P out of range");
+    DSQ_CHECK_ARG(P_reduced >= 1 && P_reduced < P, "P_reduced: between 1 and P - 1 columns");
+    DSQ_CHECK_ARG(N >= 1, "N: at least one sample");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(ldn >= N && ldx >= N && ldx_reduced >= N, "a leading dimension is smaller than N");
+    DSQ_CHECK_ARG(d_num != nullptr && d_dev != nullptr && d_s2 != nullptr, "an output pointer is null");
+    DSQ_HIP(dsq::launch_ql_dev(ctx->stream, d_y, ldn, d_sf, d_Xt, ldx, P, d_Xt_reduced, ldx_reduced, P_reduced, N, G,
+                               (double)(N - P), d_disp, d_beta, d_beta_reduced, d_num, d_dev, d_s2));
+    return DSQ_OK;
+}
+
+int dsq_dev_ql_score(dsq_ctx* ctx, const double* d_num, const double* d_s2_post, int n, int df_test, double df_total,
+                     double* d_F, double* d_pvals) {
+    DSQ_CHECK_ARG(df_test >= 1 && df_test <= DSQ_MAX_P - 1, "df_test: an integer between 1 and 127");
+    DSQ_CHECK_ARG(df_total > 0.0, "df_total: positive, or infinity for the chi-square limit");
+    DSQ_CHECK_ARG(n >= 0, "n is negative");
+    DSQ_HIP(dsq::launch_ql_score(ctx->stream, d_num, d_s2_post, n, df_test, df_total, d_F, d_pvals));
+    return DSQ_OK;
+}
+
+int dsq_dev_f_sf(dsq_ctx* ctx, const double* d_F, int n, int d1, double d2, double* d_out) {
+    DSQ_CHECK_ARG(d1 >= 1 && d1 <= DSQ_MAX_P - 1, "d1: an integer between 1 and 127");
+    DSQ_CHECK_ARG(d2 > 0.0 && std::isfinite(d2), "d2: a finite positive number");
+    DSQ_CHECK_ARG(n >= 0, "n is negative");
+    DSQ_HIP(dsq::launch_f_sf(ctx->stream, d_F, n, d1, d2, d_out));
+    return DSQ_OK;
+}
+
 int dsq_dev_rlog(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, int N, int G, const double* d_disp_fit,
                  const double* d_base_mean, double beta_prior_var, double* d_out, double* d_intercept, uint8_t* d_conv,
                  int32_t* d_niter) {

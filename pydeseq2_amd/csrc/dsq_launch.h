@@ -326,6 +326,14 @@ hipError_t launch_lrt(hipStream_t st, const int32_t* y, int ldn, const double* s
                       const double* Xr, int ldr, int Pr, int N, int G, const double* disp, const double* beta_f,
                       const double* beta_r, double* stat, double* pval);
 hipError_t launch_chisq_sf(hipStream_t st, const double* x, int n, int df, double* out);
+// ---- dsq_k_ql.hip: quasi-likelihood F-test (dsq_ql.h): deviance difference, full-model deviance and s2 = deviance / df of
+// two fits at one dispersion; F and its p-value from moderated dispersions; the F distribution's survival function
+hipError_t launch_ql_dev(hipStream_t st, const int32_t* y, int ldn, const double* sf, const double* Xf, int ldf, int Pf,
+                         const double* Xr, int ldr, int Pr, int N, int G, double df, const double* disp,
+                         const double* beta_f, const double* beta_r, double* num, double* dev, double* s2);
+hipError_t launch_ql_score(hipStream_t st, const double* num, const double* s2_post, int n, int df_test, double df_total,
+                           double* F, double* pval);
+hipError_t launch_f_sf(hipStream_t st, const double* F, int n, int d1, double d2, double* out);
 // ---- dsq_k_rlog.hip: regularized-log transformation (dsq_rlog.h): out [G][N] log2, one gene per wavefront; samples in
 // registers up to N = 512, in the output row beyond
 hipError_t launch_rlog(hipStream_t st, const int32_t* y, int ldn, const double* sf, int N, int G, const double* disp,

@@ -1347,6 +1347,15 @@ class DeseqPipeline:
 
         return lrt(self, res, reduced_design)
 
+    def ql(self, res: DeseqResult, reduced_design):
+        """Quasi-likelihood F-test of a nested reduced design (edgeR's glmQLFit / glmQLFTest) at the trend
+        dispersions of ``res``, post hoc like lrt().  Returns a pydeseq2_amd.ql.QlResult (pvalue, F, s2, s2_post, df0,
+        s02, LFC, reduced_LFC, converged, reduced_converged, ...): pydeseq2_amd.ql.ql_test.  (Single process: the
+        gene-sharded pipeline refuses it - the moderation needs the dispersions of every gene.)"""
+        from .ql import ql_test
+
+        return ql_test(self, res, reduced_design)
+
     def rlog(self, res: DeseqResult, beta_prior_var=None):
         """Regularized-log transformation (DESeq2's rlog()) of the resident counts at the trend dispersions
         of ``res``.  Returns (rlog N x G in log2, intercept, converged, n_iter, beta_prior_var): pydeseq2_amd.rlog.rlog."""
