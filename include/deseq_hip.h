@@ -511,6 +511,29 @@ int dsq_dev_ql_score(dsq_ctx* ctx, const double* d_num, const double* d_s2_post,
 /* d_out[i] = survival function of the F distribution with d1 (an integer, 1 ... 127) and d2 (real, finite, > 0)
  * degrees of freedom at d_F[i] (scipy.stats.f.sf): 1 for F <= 0, NaN for NaN. */
 int dsq_dev_f_sf(dsq_ctx* ctx, const double* d_F, int n, int d1, double d2, double* d_out);
+#define DSQ_VOOM_MAX_P 48      /* design columns of dsq_dev_voom_* */
+#define DSQ_VOOM_MAX_KNOTS 256 /* knots of the mean-variance trend of dsq_dev_voom_wls */
+/* limma-voom (Law et al. 2014; csrc/dsq_voom.h), step 1: per gene, on the counts d_y,
+ *   E_n = log2(y_n + 0.5) - d_offset[n],   d_offset[n] = log2(L_n + 1) - log2(1e6) for the library sizes L_n,
+ *   d_beta1 [G][P] = pinv(X) E (unweighted least squares through d_pinvXt, no solve),
+ *   d_sigma1 = sqrt(sum_n (E_n - x_n beta1)^2 / (N - P)),   d_amean = mean_n E_n.
+ * A gene without counts gets NaN in all three.  d_Xt, d_pinvXt: [P][ldx].
+ * DSQ_ERR_ARG: P outside 1 ... DSQ_VOOM_MAX_P, N <= P, G < 0, a leading dimension below N, a null pointer. */
+int dsq_dev_voom_fit1(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_offset, const double* d_Xt,
+                      const double* d_pinvXt, int ldx, int P, int N, int G, double* d_beta1, double* d_amean,
+                      double* d_sigma1);
+/* Step 2: per sample lambda_n = x_n beta1 + d_offset[n] and the precision weight w_n = f(lambda_n)^-4, f the piecewise-linear
+ * interpolant through the n_knots knots (d_knot_x strictly increasing, d_knot_f; constant outside them); then weighted least
+ * squares of E on X: d_beta [G][P], d_sigma2 = sum_n w_n (E_n - x_n beta)^2 / (N - P), and for each of the K contrasts
+ * (d_contrasts [K][P]) d_est [G][K] = c . beta and d_u [G][K] = sqrt(c^T (X^T W X)^-1 c), the exact unscaled standard
+ * deviation.  d_E, d_w: both non-null: the layers E and w as well, [G][ld_layers]; both null: not written.  A gene whose
+ * d_beta1 holds a NaN (no counts) gets NaN everywhere.  The knots are read back and checked: the call synchronises.
+ * DSQ_ERR_ARG: P outside 1 ... DSQ_VOOM_MAX_P, N <= P, K < 1, n_knots outside 2 ... DSQ_VOOM_MAX_KNOTS, knots not strictly
+ * increasing or not finite, G < 0, a leading dimension below N, one layer pointer without the other, a null pointer. */
+int dsq_dev_voom_wls(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_offset, const double* d_Xt, int ldx, int P,
+                     int N, int G, const double* d_beta1, const double* d_knot_x, const double* d_knot_f, int n_knots,
+                     const double* d_contrasts, int K, double* d_beta, double* d_sigma2, double* d_est, double* d_u,
+                     double* d_E, double* d_w, int ld_layers);
 /* Regularized-log transformation (DESeq2's rlog(); csrc/dsq_rlog.h): per gene the ridge-penalised NB GLM with an
  * intercept and one coefficient per sample (penalty 1 / beta_prior_var on the log2 scale, 1e-6 on the intercept), fitted by
  * IRLS from the intercept ln d_base_mean[g] at the TREND dispersion d_disp_fit[g] (deviance criterion 1e-4, at most 100

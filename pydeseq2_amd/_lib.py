@@ -216,6 +216,9 @@ def load():
           _vp, _vp, _vp)
     proto("dsq_dev_ql_score", _vp, _vp, _vp, c_int, c_int, c_double, _vp, _vp)
     proto("dsq_dev_f_sf", _vp, _vp, c_int, c_int, c_double, _vp)
+    proto("dsq_dev_voom_fit1", _vp, _vp, c_int, _vp, _vp, _vp, c_int, c_int, c_int, c_int, _vp, _vp, _vp)
+    proto("dsq_dev_voom_wls", _vp, _vp, c_int, _vp, _vp, c_int, c_int, c_int, c_int, _vp, _vp, _vp, c_int, _vp, c_int,
+          _vp, _vp, _vp, _vp, _vp, _vp, c_int)
     proto("dsq_dev_rlog", _vp, _vp, c_int, _vp, c_int, c_int, _vp, _vp, c_double, _vp, _vp, _vp, _vp)
     proto("dsq_dev_ash", _vp, _vp, _vp, c_int, c_int, c_int, _vp, _vp, c_int, c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp)
     proto("dsq_ranksum_plan", c_int, C.POINTER(c_int), C.POINTER(c_size_t))
@@ -271,6 +274,7 @@ EXPORTS = [
     "dsq_ranksum_plan", "dsq_dev_ranksum",
     "dsq_dev_log_counts", "dsq_dev_nb_residuals", "dsq_project_plan", "dsq_dev_project_out",
     "dsq_dev_ql_deviance", "dsq_dev_ql_score", "dsq_dev_f_sf",
+    "dsq_dev_voom_fit1", "dsq_dev_voom_wls",
 ]
 
 

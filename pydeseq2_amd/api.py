@@ -18,6 +18,7 @@ import numpy as np
 import pandas as pd
 
 from . import ql as _ql
+from . import voom as _voom
 from . import ranktest as _ranktest
 from . import summary as _summary
 from ._design import DesignPack
@@ -715,6 +716,22 @@ class DeseqDataSet:
             return self._pipe.vst_transform(self.obs["size_factors"].to_numpy(), **self._vst_params)
         return self._pipe.vst_transform_new(np.asarray(counts), self.logmeans, self.filtered_genes, **self._vst_params)
 
+    def voom(self, lib_size="size_factors"):
+        """The voom transformation (Law et al. 2014) of the data set's design into ``layers["voom_E"]``
+        (log2 counts per million, log2((y + 0.5) / (L + 1) 1e6)) and ``layers["voom_weights"]`` (the precision weights of
+        the mean-variance trend), for a weighted analysis elsewhere.  ``lib_size``: "size_factors" (default; the size
+        factors as effective library sizes, fitted first if they are missing), "colsums" or N positive numbers.  Genes
+        without counts get NaN columns.  ``uns["voom_knots"]`` holds the trend.  Returns (E, weights)."""
+        Xd = np.asarray(self.obsm["design_matrix"], dtype=float)
+        _voom.check_design(Xd.shape[0], Xd.shape[1], np.linalg.matrix_rank(Xd) == Xd.shape[1])
+        lib_size = _check_voom_lib_size(lib_size, self.n_obs)
+        self._need(self.obs, "size_factors", lambda: self.fit_size_factors(fit_type=self.size_factors_fit_type))
+        L = _voom.library_sizes(lib_size, self.n_obs, np.asarray(self.obs["size_factors"], dtype=float), _voom_colsums(self))
+        E, w, knots = self._pipe.voom_layers(lib_size=L)
+        self.layers["voom_E"], self.layers["voom_weights"] = E, w
+        self.uns["voom_knots"] = knots
+        return self.layers["voom_E"], self.layers["voom_weights"]
+
     def rlog(self, use_design: bool = False, fit_type=None, beta_prior_var=None):
         """Regularized-log transformation into ``layers["rlog_counts"]`` (DESeq2's ``rlog()``, which the reference does not
         have): log2 of the fitted means of a per-gene ridge-penalised GLM with one coefficient per sample,
@@ -998,6 +1015,25 @@ def _check_ql_hypothesis(lfc_null, alt_hypothesis):
                          "(use test='wald' for a thresholded or one-sided test).")
 
 
+def _check_voom_hypothesis(lfc_null, alt_hypothesis):
+    if lfc_null != 0 or alt_hypothesis is not None:
+        raise ValueError("test='voom' has no lfc_null / alt_hypothesis: limma's treat is not implemented (use test='wald' "
+                         "for a thresholded or one-sided test).")
+
+
+def _voom_colsums(dds):
+    """Exact int64 column sums (per sample) of the counts, on the host."""
+    return np.asarray(dds.X).astype(np.int64).sum(axis=1)
+
+
+def _check_voom_lib_size(lib_size, N):
+    if isinstance(lib_size, str):
+        if lib_size not in ("size_factors", "colsums"):
+            raise ValueError(f"lib_size must be 'size_factors', 'colsums' or {N} positive numbers (got {lib_size!r}).")
+        return lib_size
+    return _voom.library_sizes(lib_size, N)
+
+
 def reduced_design_matrix(dds, reduced) -> pd.DataFrame:
     """The reduced design of a likelihood-ratio test as a DataFrame over the samples of ``dds``: a formula over its
     metadata (built like the full design, same ``ref_level``), a DataFrame or a matrix.  Host only.  ValueError when it
@@ -1052,15 +1088,37 @@ class DeseqStats:
     nested model, as ``test="LRT"`` does.  ``summary()`` keeps ``log2FoldChange`` / ``lfcSE`` of the contrast, puts F in
     ``stat``, passes the p-values through the Cook's filter, independent filtering and BH, and adds ``ql_dispersion``;
     ``ql_df0`` / ``ql_s02`` hold the prior.  No ``lfc_null`` / ``alt_hypothesis``; needs N - P >= 1 and a fit with trend
-    dispersions.  Single process only."""
+    dispersions.  Single process only.
+
+    ``test="voom"`` replaces them by limma-voom (Law et al. 2014): log-CPM of the ORIGINAL counts with
+    per-observation precision weights from the mean-variance trend, a weighted least-squares fit per gene and limma's
+    moderated t of the contrast - the third standard route beside DESeq2's and edgeR's tests, and what a cohort of hundreds
+    of samples is usually analysed with.  ``lib_size``: "size_factors" (default: sf_n / geomean_n(sf_n / colsum_n), the
+    size factors as effective library sizes), "colsums" (limma's default for a matrix) or N positive numbers.
+    ``summary()`` puts the contrast's estimate in ``log2FoldChange``, sqrt(s2_post) u in ``lfcSE`` and the moderated t in
+    ``stat``, passes the p-values through independent filtering and BH - NOT through the Cook's filter, which belongs to
+    the NB fit - and adds ``voom_sigma2`` (the moderated residual variance); ``voom_df0`` / ``voom_s02`` /
+    ``voom_df_total`` / ``voom_knots`` hold the prior and the trend.  u is the exact unscaled standard deviation
+    sqrt(c' (X'WX)^-1 c), which limma's ``contrasts.fit`` only approximates for non-orthogonal designs with weights (the
+    two agree for single-coefficient contrasts).  No ``lfc_null`` / ``alt_hypothesis`` (limma's ``treat``), ``reduced=`` or
+    ``strata=``; designs of at most 48 columns, of full rank, with N - P >= 1.  Single process only."""
 
     def __init__(self, dds: DeseqDataSet, contrast, alpha=0.05, cooks_filter=True, independent_filter=True,
                  prior_LFC_var=None, lfc_null=0.0, alt_hypothesis=None, inference=None, quiet=True, n_cpus=None, *,
-                 test="wald", reduced=None, strata=None):
-        if test not in ("wald", "LRT", "wilcoxon", "QL"):
+                 test="wald", reduced=None, strata=None, lib_size="size_factors"):
+        if test not in ("wald", "LRT", "wilcoxon", "QL", "voom"):
             raise ValueError(f"test must be 'wald' or 'LRT', or 'wilcoxon' for the rank-sum test, or 'QL' for the "
-                             f"quasi-likelihood F-test (got {test!r}).")
+                             f"quasi-likelihood F-test, or 'voom' for limma-voom (got {test!r}).")
         self.test, self.reduced_design, self.strata = test, None, None
+        if test == "voom":  # (host-only checks: before anything touches the GPU)
+            _check_voom_hypothesis(lfc_null, alt_hypothesis)
+            if reduced is not None or strata is not None:
+                raise ValueError("test='voom' tests a contrast of the full design: it takes no reduced= and no strata=.")
+            Xd = np.asarray(dds.obsm["design_matrix"], dtype=float)
+            _voom.check_design(Xd.shape[0], Xd.shape[1], np.linalg.matrix_rank(Xd) == Xd.shape[1])
+            self.lib_size = _check_voom_lib_size(lib_size, Xd.shape[0])
+        elif not (isinstance(lib_size, str) and lib_size == "size_factors"):
+            raise ValueError("lib_size is the library size of limma-voom: pass test='voom' with it.")
         if test == "wilcoxon":  # (host-only checks: before anything touches the GPU)
             _ranktest.check_alternative(alt_hypothesis, lfc_null)
             if contrast is not None and (isinstance(contrast, np.ndarray) or not isinstance(contrast[0], str)):
@@ -1174,6 +1232,15 @@ class DeseqStats:
         ``alt_hypothesis``): every contrast a ``[factor, tested, ref]`` list; the rank-sum tests of all of them run in
         one launch (``DeseqPipeline.ranksum``) after the Wald launch that gives ``lfcSE``.  Single process only: the
         distributed pipeline has no multi-contrast launch."""
+        if kwargs.get("test", "wald") == "voom":  # all contrasts on one pair of launches
+            contrasts = list(contrasts)
+            if not contrasts:
+                raise ValueError("DeseqStats.batch() needs at least one contrast.")
+            out = [cls(dds, c, **kwargs) for c in contrasts]
+            r = out[0]._voom_call(np.stack([o.contrast_vector for o in out]))
+            for k, o in enumerate(out):
+                o._set_voom(r, k)
+            return out
         if kwargs.get("test", "wald") == "QL":
             raise ValueError("DeseqStats.batch() runs Wald tests: test='QL' fits a reduced design per contrast (use "
                              "DeseqStats(dds, contrast, test='QL') for each).")
@@ -1251,6 +1318,34 @@ class DeseqStats:
         if hasattr(self, "padj"):
             del self.padj
 
+    def _voom_call(self, contrasts):
+        pipe, res = self.dds._pipe, self.dds._res
+        L = _voom.library_sizes(self.lib_size, pipe.N, res.size_factors, _voom_colsums(self.dds))
+        return pipe.voom(res, contrasts, L)
+
+    def _set_voom(self, r, k):
+        idx = self.dds.var_names
+        self.p_values, self.statistics = pd.Series(r.pvalue[k], index=idx), pd.Series(r.t[k], index=idx)
+        self.voom_est, self.voom_lfcSE = pd.Series(r.est[k], index=idx), pd.Series(r.lfcSE[k], index=idx)
+        self.voom_sigma2, self.voom_sigma2_raw = pd.Series(r.s2_post, index=idx), pd.Series(r.sigma2, index=idx)
+        self.voom_df0, self.voom_s02, self.voom_df_total = float(r.df0), float(r.s02), float(r.df_total)
+        self.voom_knots = r.knots
+        self.voom_LFC = pd.DataFrame(r.beta, index=idx, columns=self.LFC.columns)
+        self.voom_Amean = pd.Series(r.Amean, index=idx)
+        self._wald_key = ("voom",)
+        if hasattr(self, "padj"):
+            del self.padj
+
+    def run_voom_test(self):
+        """limma-voom of the contrast (``DeseqPipeline.voom``): ``statistics`` (the moderated t) and ``p_values`` are the
+        test's; also ``voom_est`` (log2), ``voom_lfcSE``, ``voom_sigma2`` (moderated) / ``voom_sigma2_raw``, ``voom_df0`` /
+        ``voom_s02`` / ``voom_df_total`` (the prior), ``voom_knots`` (the trend), ``voom_LFC`` (the weighted fit, log2) and
+        ``voom_Amean``."""
+        if self.test != "voom":
+            raise ValueError("run_voom_test() needs DeseqStats(..., test='voom').")
+        _check_voom_hypothesis(self.lfc_null, self.alt_hypothesis)
+        self._set_voom(self._voom_call(self.contrast_vector[None, :]), 0)
+
     def run_ranksum_test(self):
         """Wilcoxon rank-sum test of the contrast's two levels (``DeseqPipeline.ranksum``): ``statistics`` (the z
         statistic), ``p_values`` and ``auc`` (the probability that a tested sample lies above a reference sample of its
@@ -1297,6 +1392,8 @@ class DeseqStats:
         if self.test in ("LRT", "QL"):
             (_check_lrt_hypothesis if self.test == "LRT" else _check_ql_hypothesis)(
                 kwargs.get("lfc_null", self.lfc_null), kwargs.get("alt_hypothesis", self.alt_hypothesis))
+        if self.test == "voom":
+            _check_voom_hypothesis(kwargs.get("lfc_null", self.lfc_null), kwargs.get("alt_hypothesis", self.alt_hypothesis))
         self.lfc_null = kwargs.get("lfc_null", self.lfc_null)
         self.alt_hypothesis = kwargs.get("alt_hypothesis", self.alt_hypothesis)
         if self.test == "LRT":
@@ -1310,10 +1407,14 @@ class DeseqStats:
             _check_ql_hypothesis(self.lfc_null, self.alt_hypothesis)
             if getattr(self, "_wald_key", None) != ("QL",):
                 self.run_ql_test()
+        elif self.test == "voom":
+            if getattr(self, "_wald_key", None) != ("voom",):
+                self.run_voom_test()
         elif not hasattr(self, "p_values") or getattr(self, "_wald_key", None) != (self.lfc_null, self.alt_hypothesis):
             self.run_wald_test()
         if not hasattr(self, "padj"):
-            if self.cooks_filter and self.test != "wilcoxon":  # (rank-based: no Cook's filter, see the class)
+            # (rank-based, or a fit of its own on the original counts: no Cook's filter, see the class)
+            if self.cooks_filter and self.test not in ("wilcoxon", "voom"):
                 self._cooks_filtering()
             if self.independent_filter:
                 self._independent_filtering()
@@ -1324,12 +1425,17 @@ class DeseqStats:
         df["log2FoldChange"] = self.LFC.to_numpy() @ self.contrast_vector / np.log(2)
         if getattr(self, "ash_LFC", None) is not None:  # (adaptive shrinkage of the contrast: kept, like apeGLM's column)
             df["log2FoldChange"] = self.ash_LFC / np.log(2)
-        df["lfcSE"] = self.SE / np.log(2)
+        if self.test == "voom":  # (the weighted fit's own estimate and standard error, already base 2)
+            df["log2FoldChange"], df["lfcSE"] = self.voom_est, self.voom_lfcSE
+        else:
+            df["lfcSE"] = self.SE / np.log(2)
         df["stat"], df["pvalue"], df["padj"] = self.statistics, self.p_values, self.padj
         if self.test == "wilcoxon":
             df["auc"] = self.auc
         if self.test == "QL":
             df["ql_dispersion"] = self.ql_dispersion
+        if self.test == "voom":
+            df["voom_sigma2"] = self.voom_sigma2
         if getattr(self, "_ash_svalue", False):
             df["svalue"] = self.svalues
         self.results_df = df

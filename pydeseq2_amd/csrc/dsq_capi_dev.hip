@@ -661,6 +661,50 @@ int dsq_dev_f_sf(dsq_ctx* ctx, const double* d_F, int n, int d1, double d2, doub
     return DSQ_OK;
 }
 
+int dsq_dev_voom_fit1(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_offset, const double* d_Xt,
+                      const double* d_pinvXt, int ldx, int P, int N, int G, double* d_beta1, double* d_amean,
+                      double* d_sigma1) {
+    DSQ_CHECK_ARG(P >= 1 && P <= DSQ_VOOM_MAX_P, "P: between 1 and 48 design columns");
+    DSQ_CHECK_ARG(N > P, "N: more samples than design columns (residual degrees of freedom)");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(ldn >= N && ldx >= N, "a leading dimension is smaller than N");
+    DSQ_CHECK_ARG(d_beta1 != nullptr && d_amean != nullptr && d_sigma1 != nullptr, "an output pointer is null");
+    if (G == 0) return DSQ_OK;
+    DSQ_CHECK_ARG(d_y != nullptr && d_offset != nullptr && d_Xt != nullptr && d_pinvXt != nullptr, "an input pointer is null");
+    DSQ_HIP(dsq::launch_voom_fit1(ctx->stream, d_y, ldn, d_offset, d_Xt, d_pinvXt, ldx, P, N, G, d_beta1, d_amean, d_sigma1));
+    return DSQ_OK;
+}
+
+int dsq_dev_voom_wls(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_offset, const double* d_Xt, int ldx, int P,
+                     int N, int G, const double* d_beta1, const double* d_knot_x, const double* d_knot_f, int n_knots,
+                     const double* d_contrasts, int K, double* d_beta, double* d_sigma2, double* d_est, double* d_u,
+                     double* d_E, double* d_w, int ld_layers) {
+    DSQ_CHECK_ARG(P >= 1 && P <= DSQ_VOOM_MAX_P, "P: between 1 and 48 design columns");
+    DSQ_CHECK_ARG(N > P, "N: more samples than design columns (residual degrees of freedom)");
+    DSQ_CHECK_ARG(K >= 1, "K: at least one contrast");
+    DSQ_CHECK_ARG(n_knots >= 2 && n_knots <= DSQ_VOOM_MAX_KNOTS, "n_knots: between 2 and 256 knots");
+    DSQ_CHECK_ARG(G >= 0, "G is negative");
+    DSQ_CHECK_ARG(ldn >= N && ldx >= N, "a leading dimension is smaller than N");
+    DSQ_CHECK_ARG((d_E == nullptr) == (d_w == nullptr), "the layers E and w: both or neither");
+    DSQ_CHECK_ARG(d_E == nullptr || ld_layers >= N, "ld_layers is smaller than N");
+    DSQ_CHECK_ARG(d_beta != nullptr && d_sigma2 != nullptr && d_est != nullptr && d_u != nullptr, "an output pointer is null");
+    DSQ_CHECK_ARG(d_knot_x != nullptr && d_knot_f != nullptr && d_contrasts != nullptr, "an input pointer is null");
+    double hk[2 * DSQ_VOOM_MAX_KNOTS];
+    DSQ_HIP(hipMemcpyAsync(hk, d_knot_x, (size_t)n_knots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    DSQ_HIP(hipMemcpyAsync(hk + DSQ_VOOM_MAX_KNOTS, d_knot_f, (size_t)n_knots * sizeof(double), hipMemcpyDeviceToHost,
+                           ctx->stream));
+    DSQ_HIP(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < n_knots; ++i) {
+        DSQ_CHECK_ARG(std::isfinite(hk[i]) && std::isfinite(hk[DSQ_VOOM_MAX_KNOTS + i]), "a knot is not finite");
+        DSQ_CHECK_ARG(i == 0 || hk[i] > hk[i - 1], "the knots are not strictly increasing");
+    }
+    if (G == 0) return DSQ_OK;
+    DSQ_CHECK_ARG(d_y != nullptr && d_offset != nullptr && d_Xt != nullptr && d_beta1 != nullptr, "an input pointer is null");
+    DSQ_HIP(dsq::launch_voom_wls(ctx->stream, d_y, ldn, d_offset, d_Xt, ldx, P, N, G, d_beta1, d_knot_x, d_knot_f, n_knots,
+                                 d_contrasts, K, d_beta, d_sigma2, d_est, d_u, d_E, d_w, ld_layers));
+    return DSQ_OK;
+}
+
 int dsq_dev_rlog(dsq_ctx* ctx, const int32_t* d_y, int ldn, const double* d_sf, int N, int G, const double* d_disp_fit,
                  const double* d_base_mean, double beta_prior_var, double* d_out, double* d_intercept, uint8_t* d_conv,
                  int32_t* d_niter) {

@@ -334,6 +334,16 @@ hipError_t launch_ql_dev(hipStream_t st, const int32_t* y, int ldn, const double
 hipError_t launch_ql_score(hipStream_t st, const double* num, const double* s2_post, int n, int df_test, double df_total,
                            double* F, double* pval);
 hipError_t launch_f_sf(hipStream_t st, const double* F, int n, int d1, double d2, double* out);
+// ---- dsq_k_voom.hip: limma-voom (dsq_voom.h): the first fit (log-CPM, unweighted least squares, sigma1 and Abar: the points
+// of the mean-variance trend) and the weighted fit with precision weights from the trend's knot table (nk <= kVoomMaxKnots),
+// K contrasts [K][P]; off [N] = log2(L + 1) - log2(1e6); P <= kWideMaxP; E_out / w_out [G][ldl] or both null
+hipError_t launch_voom_fit1(hipStream_t st, const int32_t* y, int ldn, const double* off, const double* Xt,
+                            const double* pinvXt, int ldx, int P, int N, int G, double* beta1, double* amean,
+                            double* sigma1);
+hipError_t launch_voom_wls(hipStream_t st, const int32_t* y, int ldn, const double* off, const double* Xt, int ldx, int P,
+                           int N, int G, const double* beta1, const double* knot_x, const double* knot_f, int nk,
+                           const double* contrasts, int K, double* beta, double* sigma2, double* est, double* u,
+                           double* E_out, double* w_out, int ldl);
 // ---- dsq_k_rlog.hip: regularized-log transformation (dsq_rlog.h): out [G][N] log2, one gene per wavefront; samples in
 // registers up to N = 512, in the output row beyond
 hipError_t launch_rlog(hipStream_t st, const int32_t* y, int ldn, const double* sf, int N, int G, const double* disp,

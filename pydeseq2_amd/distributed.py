@@ -466,6 +466,10 @@ class DistDeseqPipeline(DeseqPipeline):
         raise ValueError("test='QL': the gene-sharded pipeline has no quasi-likelihood test (the moderation needs the "
                          "quasi-likelihood dispersions of the genes of every rank); run it in a single process.")
 
+    def voom(self, res, contrasts, lib_size="size_factors"):
+        raise ValueError("test='voom': the gene-sharded pipeline has no voom (the mean-variance trend and the prior of the "
+                         "moderated t need the genes of every rank); run it in a single process.")
+
     def _all_genes_host(self, d_vec, n):
         """The ranks' per-gene vectors concatenated in rank order (iterative size factors: the trimmed mean of the
         dispersions and the objective's quantile / sum run over the genes of all ranks, dds.py:1460-1548).  One

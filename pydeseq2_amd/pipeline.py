@@ -1356,6 +1356,31 @@ class DeseqPipeline:
 
         return ql_test(self, res, reduced_design)
 
+    def voom_lib_sizes(self, lib_size, size_factors=None):
+        """The library sizes of voom (pydeseq2_amd.voom.library_sizes) for "size_factors", "colsums" or N numbers; the
+        column sums - exact int64 sums on the host - are taken once from the resident sample-major counts."""
+        from .voom import library_sizes
+
+        if isinstance(lib_size, str) and getattr(self, "_voom_colsums", None) is None:
+            self._voom_colsums = self.d_raw.to_host().astype(np.int64).sum(axis=1)
+        return library_sizes(lib_size, self.N, size_factors, getattr(self, "_voom_colsums", None))
+
+    def voom(self, res: DeseqResult, contrasts, lib_size="size_factors"):
+        """limma-voom (Law et al. 2014) of K contrasts (K x P, or one vector) on the resident ORIGINAL
+        counts, post hoc: log-CPM with precision weights from the mean-variance trend, a weighted least-squares fit per
+        gene, limma's moderated t.  ``lib_size``: "size_factors" (the size factors of ``res`` as effective library sizes),
+        "colsums" or N positive numbers.  Returns a pydeseq2_amd.voom.VoomResult: pydeseq2_amd.voom.voom_test.  (Single
+        process: the gene-sharded pipeline refuses it - the trend and the prior need the genes of every rank.)"""
+        from .voom import voom_test
+
+        return voom_test(self, res, contrasts, self.voom_lib_sizes(lib_size, res.size_factors))
+
+    def voom_layers(self, size_factors=None, lib_size="size_factors"):
+        """The voom transformation alone: (E, weights, knots), E and weights N x G: pydeseq2_amd.voom.voom_layers."""
+        from .voom import voom_layers
+
+        return voom_layers(self, self.voom_lib_sizes(lib_size, size_factors))
+
     def rlog(self, res: DeseqResult, beta_prior_var=None):
         """Regularized-log transformation (DESeq2's rlog()) of the resident counts at the trend dispersions
         of ``res``.  Returns (rlog N x G in log2, intercept, converged, n_iter, beta_prior_var): pydeseq2_amd.rlog.rlog."""
